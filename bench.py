@@ -15,7 +15,9 @@ only collective is ONE all-reduce (RCCL) of the per-rank NMSE accumulators
 after the timed region, as in the reference's Monte-Carlo average
 (Proposed_method_NMSEvsTp.py:176).
 
-Also reported (one JSON line on rank 0):
+A plain run sets up, warms up, times the steps, writes the last step's theta under
+--dump-outputs DIR and prints the result line (one JSON line on rank 0) with the NMSE the metric
+names.  With --full the line also holds:
   roofline      the M-step (the dominant phase per EM iteration; "kernels" lists the
                 launches it consists of) timed live with HIP events on the launch
                 stream: algorithmic flops per launch / time, peak = FP64
@@ -389,6 +391,30 @@ def launch_ranks(n, argv, timeout=None):
     return bad[0] if bad else 0
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, tensors, rank=0, world=1):
+    """--dump-outputs: the device tensors the timed path left (name -> tensor) as
+    path/<name>.npy in float64 (complex ones with a trailing re / im axis; multi-rank runs add
+    _rank<r> to the name).  Past DUMP_BUDGET_BYTES in all, every array keeps the same fraction of
+    its leading-axis rows (its trials), drawn once from a fixed seed."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        t = torch.view_as_real(t) if t.is_complex() else t
+        arrays[name] = t.detach().to(torch.float64).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            # one seed per array: arrays over the same trials keep the same rows
+            n = max(1, int(a.shape[0] * DUMP_BUDGET_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+                np.ascontiguousarray(a))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -408,7 +434,14 @@ def parse_args(argv=None):
                     help="E-step (default: the workload's, ESTEP)")
     ap.add_argument("--partition-r", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel "
+                         "timings and rooflines, the status counts and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (theta, status, "
+                         "iterations done) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--kernel-reps", type=int, default=5)
     ap.add_argument("--roofline-only", action="store_true",
                     help="cfg5: only the roofline launches (the largest T_d point's E-steps and "
@@ -764,6 +797,12 @@ def grid_main(args, ranks, pkg):
     torch.cuda.synchronize()
     ranks.barrier()
     elapsed = ranks.max_time(time.perf_counter() - t0)
+    if args.dump_outputs:
+        out = {}
+        for di, k, js, eng in engines:
+            tag = f"{dets[di]}_td{T_D[k]}" + (f"_snr{js[0]}" if len(js) == 1 else "")
+            out["theta_" + tag], out["iters_done_" + tag] = eng.theta, eng.iters_done
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     # executed trial-iterations of one step (every step repeats the same EMs from theta_0)
     done = torch.stack([eng.iters_done.sum() for _, _, _, eng in engines]).sum().to(torch.float64)
@@ -781,8 +820,6 @@ def grid_main(args, ranks, pkg):
     a = acc[:-1].view(nd, nt, ns, 2).cpu().numpy()
     mean = a[..., 0] / a[..., 1]
     executed = float(acc[-1].item())
-    flagged = sum(int((eng.status != 0).sum().item()) for _, _, _, eng in engines)
-    roof = grid_roofline(args, g, engines, len(T_D) - 1, torch)   # overwrites theta: after NMSE
     line = {
         "metric": metric_name(n_tx, N, T_p, f"{T_D[0]}..{T_D[-1]}") + " (SNR x T_d grid, five EMs)",
         "value": executed * args.steps / elapsed,
@@ -809,11 +846,14 @@ def grid_main(args, ranks, pkg):
         "nominal_iterations_per_step": nominal * world,
         "nmse_grid_mean": {det: float(np.mean(mean[di])) for di, det in enumerate(dets)},
         "nmse_at_max_td": {det: [float(v) for v in mean[di, -1]] for di, det in enumerate(dets)},
-        "status_flagged_trials": flagged,
-        "roofline": roof["roofline"],
-        "phases_at_max_td": roof["phases"],
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["status_flagged_trials"] = sum(int((eng.status != 0).sum().item())
+                                            for _, _, _, eng in engines)
+        roof = grid_roofline(args, g, engines, len(T_D) - 1, torch)   # overwrites theta: after NMSE
+        line["roofline"] = roof["roofline"]
+        line["phases_at_max_td"] = roof["phases"]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = grid_cpu_baseline(g, args.seed)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -880,12 +920,60 @@ def main(argv=None):
     torch.cuda.synchronize()
     ranks.barrier()
     elapsed = ranks.max_time(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"theta": eng.theta, "status": eng.status}, rank, world)
 
     # ---- the one collective: Monte-Carlo NMSE accumulators (sum NMSE, count) ----
     nm = eng.nmse()
     acc = torch.stack([nm.sum(), torch.tensor(float(B), dtype=torch.float64, device="cuda")])
     ranks.allreduce_sum(acc)
     nmse_mean = float(acc[0] / acc[1])
+
+    line = {
+        "metric": metric_name(n_tx, N, T_p, T_d),
+        "value": world * B * iters * args.steps / elapsed,
+        "unit": "EM-iterations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (Rayleigh channels, 16-QAM, uniform RIS phases, CN noise; numpy Generator)",
+        "config": {"workload": args.config, "n_tx": n_tx, "n_rx": n_rx, "N_RIS": N, "T_p": T_p,
+                   "T_d": T_d, "M": M, "trials_per_gpu": B, "em_iters": iters,
+                   "snr_db": args.snr, "estep": mode, "partition_r": part_r, "solve": solve,
+                   "parallelism": f"trials-sharded x{world}",
+                   "streams_per_gpu": len(eng.subs) or 1,
+                   "rccl_init": args.rccl_init if ranks.dist is not None else None},
+        "schedule": (f"per GPU: {len(eng.subs)} contiguous sub-batches of the {B} trials, one sbce_em "
+                     f"each on its own HIP stream (bitwise the same theta as one call)"
+                     + ("; kernels_ms and the rooflines time whole-batch launches alone"
+                        if args.full else "") if eng.subs else
+                     "one sbce_em call per GPU"),
+        "nmse_mean": nmse_mean,
+        "nmse_note": ("at cfg 1 / 20 dB the EM moves the pilot-only theta_0 (NMSE ~0.93) to NMSE "
+                      "~9 within ~4 iterations; the 20-iteration trajectory is pinned to the float64 "
+                      "oracle (tests/golden/cfg1_traj.npz), which is validated against the reference "
+                      "em() itself at this kernel shape for 2 iterations (cfg1_kernel.npz)"
+                      if args.config == "cfg1" else None),
+    }
+    if args.full:
+        line.update(full_figures(args, pkg, eng, cfg, mode, part_r, solve, varn,
+                                 cpu=rank == 0 and world == 1 and not args.no_cpu_baseline))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    ranks.close()
+
+
+def full_figures(args, pkg, eng, cfg, mode, part_r, solve, varn, cpu):
+    """--full, after the timed steps and the NMSE collective (the launches here overwrite theta):
+    the status counts, the E-step / M-step / R build / Cholesky launches timed alone with HIP
+    events and their rooflines, and (cpu) the CPU baselines, as keys of the result line."""
+    import torch
+    n_tx, n_rx, N, T_p, T_d, M, B, iters = cfg
     # SBCE_STATUS_NONHPD only: the PILOT / DETECTOR bits are informational
     nonhpd = int(((eng.status & pkg._lib.SBCE_STATUS_NONHPD) != 0).sum().item())
     status_bits = {name: int(((eng.status & bit) != 0).sum().item())
@@ -1109,36 +1197,7 @@ def main(argv=None):
     # M-step phase
     roofline = rb_roof if rb_roof is not None and n_tx * P <= 512 else mstep_roof
 
-    value = world * B * iters * args.steps / elapsed
     line = {
-        "metric": metric_name(n_tx, N, T_p, T_d),
-        "value": value,
-        "unit": "EM-iterations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (Rayleigh channels, 16-QAM, uniform RIS phases, CN noise; numpy Generator)",
-        "config": {"workload": args.config, "n_tx": n_tx, "n_rx": n_rx, "N_RIS": N, "T_p": T_p,
-                   "T_d": T_d, "M": M, "trials_per_gpu": B, "em_iters": iters,
-                   "snr_db": args.snr, "estep": mode, "partition_r": part_r, "solve": solve,
-                   "parallelism": f"trials-sharded x{world}",
-                   "streams_per_gpu": len(eng.subs) or 1,
-                   "rccl_init": args.rccl_init if ranks.dist is not None else None},
-        "schedule": (f"per GPU: {len(eng.subs)} contiguous sub-batches of the {B} trials, one sbce_em "
-                     f"each on its own HIP stream (bitwise the same theta as one call); kernels_ms "
-                     f"and the rooflines time whole-batch launches alone" if eng.subs else
-                     "one sbce_em call per GPU"),
-        "nmse_mean": nmse_mean,
-        "nmse_note": ("at cfg 1 / 20 dB the EM moves the pilot-only theta_0 (NMSE ~0.93) to NMSE "
-                      "~9 within ~4 iterations; the 20-iteration trajectory is pinned to the float64 "
-                      "oracle (tests/golden/cfg1_traj.npz), which is validated against the reference "
-                      "em() itself at this kernel shape for 2 iterations (cfg1_kernel.npz)"
-                      if args.config == "cfg1" else None),
         "nonhpd_trials": nonhpd,
         "status_trials": status_bits,
         "kernels_ms": {"estep": estep_ms, "mstep_build_plus_solve": mstep_ms},
@@ -1148,15 +1207,13 @@ def main(argv=None):
         "chol_roofline": chol_roof,
         "estep_roofline": estep_roof,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if cpu:
         line["cpu_baseline"] = cpu_baseline(cfg, varn, args.seed,
                                             iters=2 if args.config in ("cfg1", "plumbing") else 1,
                                             mode=mode, part_r=part_r)
         line["cpu_baseline_reference_structured"] = cpu_baseline_reference_structured(
             cfg, varn, args.seed, mode=mode, part_r=part_r)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    ranks.close()
+    return line
 
 
 if __name__ == "__main__":

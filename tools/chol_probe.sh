@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 1 --warmup 0 --iters 3 --kernel-reps 1 --no-cpu-baseline --streams 1"
+B="$R/bench.py --full --steps 1 --warmup 0 --iters 3 --kernel-reps 1 --no-cpu-baseline --streams 1"
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
     SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS GRBM_GUI_ACTIVE \
     -d "$O/sq" -o run -- python3 $B > "$O/sq.log" 2>&1

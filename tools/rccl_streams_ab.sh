@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29512
-B="python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --kernel-reps 1"
+B="python3 $R/bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --kernel-reps 1"
 timeout -k 10 120 $B --streams 3 > "$O/plain_s3.log" 2>&1
 for INIT in lazy eager; do
   for S in 3 1; do
