@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define SBCE_ABI_VERSION 6
+#define SBCE_ABI_VERSION 7
 
 /* return codes */
 #define SBCE_OK 0
@@ -122,6 +122,9 @@ extern "C" {
 #define SBCE_STATUS_RANK 16     /* SBCE_SOLVE_MINNORM: a Cholesky pivot lay between 4x lstsq's
                                    rank cut and 2048x it, where the pivot-based rank may differ
                                    from the singular-value rank np.linalg.lstsq uses */
+#define SBCE_STATUS_SINGULAR 32 /* sbce_approx_em: a pivot of the N x N normal matrix A was
+                                   <= 1e-14 max_i |A_ii| (A singular: T_p + T_d < N); the trial
+                                   stopped there and g holds its last finite iterate */
 
 typedef struct sbce_dims {
     int32_t batch;      /* B: independent Monte-Carlo trials */
@@ -222,6 +225,53 @@ int sbce_gauss_expand(const sbce_dims* d, const void* theta, void* h_out, void* 
 /* Per-trial NMSE ||theta - h||^2 / ||h||^2 (Proposed_method_NMSEvsTp.py:172). */
 int sbce_nmse(const sbce_dims* d, const void* theta, const void* h_true,
               double* nmse_out, void* hip_stream);
+
+/* ---- Semi-blind Gaussian-approximation EM (ABI 7): the comparator EM_approx of
+ * "Comparision/Comparision T_d vs NMSE.py":106-145 (the same function at "Comparision/
+ * Comparision T_p .py":74-113).  Model y_t = G^H psi_t x_t + z_t with G n_ris x n_rx, scalar
+ * symbols (n_tx = 1), no direct path.  sbce_dims / sbce_ptrs are not used by these two entry
+ * points.  Batch-major layouts, complex128:
+ *   y_d   [B][T_d][n_rx]   reference Y_d (n_rx x L_d), transposed
+ *   y_p   [B][T_p][n_rx]   reference Y_p (n_rx x L_p), transposed
+ *   psi_d [B][T_d][n_ris]  reference PsiTilde_td (N x L_d), transposed
+ *   psi_p [B][T_p][n_ris]  reference PsiTilde_tp (N x L_p), transposed
+ *   x_p   [B][T_p]         pilot symbols
+ *   g     [B][n_ris][n_rx] in: G_0 = conj(Y_p pinv(Psi_p diag(x_p)))^T (:107-108, computed by
+ *                          the caller); out: the estimate after `iters` updates */
+typedef struct sbce_approx_dims {
+    int32_t batch;      /* B: independent trials */
+    int32_t n_ris;      /* N: RIS elements (1..64) */
+    int32_t n_rx;       /* M: receive antennas (1..8) */
+    int32_t t_p;        /* pilot symbols (>= 1) */
+    int32_t t_d;        /* data symbols (>= 1) */
+    int32_t reserved;   /* 0 */
+    double varn;        /* noise variance parameter; the estimator uses varn^2 (:124, :128) */
+} sbce_approx_dims;
+
+typedef struct sbce_approx_ptrs {
+    const void* y_d;
+    const void* y_p;
+    const void* psi_d;
+    const void* psi_p;
+    const void* x_p;
+    void* g;
+    const double* varn_t;   /* may be NULL: [B] per-trial varn, as sbce_ptrs.varn_t */
+    int32_t* status;        /* may be NULL: [B] SBCE_STATUS_* (SBCE_STATUS_SINGULAR) */
+    void* workspace;        /* may be NULL when sbce_approx_workspace_bytes reports 0 */
+    size_t workspace_bytes;
+} sbce_approx_ptrs;
+
+/* Device workspace of sbce_approx_em for `d` (0 in this version: the state of a trial lives in
+ * LDS and registers). */
+int sbce_approx_workspace_bytes(const sbce_approx_dims* d, size_t* bytes);
+
+/* `iters` updates of the Gaussian-approximation EM on every trial, in one kernel launch (the
+ * reference's `while i <= Iterations` performs Iterations + 1 updates).  A trial whose normal
+ * matrix is singular gets SBCE_STATUS_SINGULAR and keeps its last finite iterate; the call
+ * still returns 0.  SBCE_EINVAL: null required pointer, varn <= 0, iters < 1, batch < 1,
+ * t_p < 1, t_d < 1; SBCE_EUNSUPPORTED: n_ris > 64 or n_rx > 8 (checked before any HIP call). */
+int sbce_approx_em(const sbce_approx_dims* d, const sbce_approx_ptrs* p, int iters,
+                   void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libsbce.so")
 # only by debug_env() (tests' cross-checks, tools), never by the product path
 AB_LIB_PATH = os.path.join(_HERE, "libsbce_ab.so")
 
-SBCE_ABI_VERSION = 6
+SBCE_ABI_VERSION = 7
 SBCE_ESTEP_SOFT = 0
 SBCE_ESTEP_HARD = 1
 SBCE_ESTEP_PM = 2
@@ -30,10 +30,12 @@ SBCE_STATUS_PILOT = 2
 SBCE_STATUS_DETECTOR = 4
 SBCE_STATUS_DEBUG = 8
 SBCE_STATUS_RANK = 16
+SBCE_STATUS_SINGULAR = 32
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_workspace_bytes_solve", "sbce_em",
-            "sbce_estep", "sbce_mstep", "sbce_ser", "sbce_gauss_expand", "sbce_nmse")
+            "sbce_estep", "sbce_mstep", "sbce_ser", "sbce_gauss_expand", "sbce_nmse",
+            "sbce_approx_workspace_bytes", "sbce_approx_em")
 
 
 class SbceUnavailable(RuntimeError):
@@ -59,6 +61,20 @@ class Ptrs(ctypes.Structure):
                 ("status", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
                 ("workspace_bytes", ctypes.c_size_t), ("x_dest", ctypes.c_void_p),
                 ("x_sup", ctypes.c_void_p), ("varn_t", ctypes.c_void_p)]
+
+
+class ApproxDims(ctypes.Structure):
+    """sbce_approx_dims (include/sbce.h): the Gaussian-approximation comparator EM."""
+    _fields_ = [("batch", ctypes.c_int32), ("n_ris", ctypes.c_int32), ("n_rx", ctypes.c_int32),
+                ("t_p", ctypes.c_int32), ("t_d", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("varn", ctypes.c_double)]
+
+
+class ApproxPtrs(ctypes.Structure):
+    _fields_ = [("y_d", ctypes.c_void_p), ("y_p", ctypes.c_void_p), ("psi_d", ctypes.c_void_p),
+                ("psi_p", ctypes.c_void_p), ("x_p", ctypes.c_void_p), ("g", ctypes.c_void_p),
+                ("varn_t", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
 _lib = None
@@ -112,6 +128,12 @@ def load(path=None):
     lib.sbce_nmse.restype = ctypes.c_int
     lib.sbce_nmse.argtypes = [ctypes.POINTER(Dims), ctypes.c_void_p, ctypes.c_void_p,
                               ctypes.c_void_p, ctypes.c_void_p]
+    lib.sbce_approx_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_approx_workspace_bytes.argtypes = [ctypes.POINTER(ApproxDims),
+                                                ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_approx_em.restype = ctypes.c_int
+    lib.sbce_approx_em.argtypes = [ctypes.POINTER(ApproxDims), ctypes.POINTER(ApproxPtrs),
+                                   ctypes.c_int, ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

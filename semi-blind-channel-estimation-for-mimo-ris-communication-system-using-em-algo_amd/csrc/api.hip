@@ -571,4 +571,32 @@ int sbce_nmse(const sbce_dims* d, const void* theta, const void* h_true, double*
                               (hipStream_t)hip_stream));
 }
 
+int sbce_approx_workspace_bytes(const sbce_approx_dims* d, size_t* bytes) {
+    if (!d || !bytes) return SBCE_EINVAL;
+    *bytes = 0;                          // a trial's state lives in LDS and registers
+    return SBCE_OK;
+}
+
+int sbce_approx_em(const sbce_approx_dims* d, const sbce_approx_ptrs* p, int iters,
+                   void* hip_stream) {
+    if (!d || !p) return SBCE_EINVAL;
+    if (d->batch < 1 || d->n_ris < 1 || d->n_rx < 1 || d->t_p < 1 || d->t_d < 1 || iters < 1 ||
+        !(d->varn > 0.0))
+        return SBCE_EINVAL;
+    const void* req[] = {p->y_d, p->y_p, p->psi_d, p->psi_p, p->x_p, p->g};
+    for (const void* q : req)
+        if (!q || !aligned16(q)) return SBCE_EINVAL;
+    if (p->varn_t && ((uintptr_t)p->varn_t & 7)) return SBCE_EINVAL;
+    if (!approx_supported(d->n_ris, d->n_rx)) return SBCE_EUNSUPPORTED;
+    clear_stale_error();
+    ApproxArgs a;
+    a.yd = (const cd*)p->y_d; a.yp = (const cd*)p->y_p; a.psid = (const cd*)p->psi_d;
+    a.psip = (const cd*)p->psi_p; a.xp = (const cd*)p->x_p; a.g = (cd*)p->g;
+    a.varn_t = p->varn_t; a.status = p->status;
+    a.B = d->batch; a.N = d->n_ris; a.M = d->n_rx; a.Tp = d->t_p; a.Td = d->t_d; a.iters = iters;
+    a.varn = d->varn;
+    a.status0 = debug_nondefault() ? SBCE_STATUS_DEBUG : 0;
+    return hip_rc(launch_approx(a, (hipStream_t)hip_stream));
+}
+
 }  // extern "C"

@@ -488,4 +488,21 @@ hipError_t launch_em_init(int B, int32_t* done, int32_t* status, int status_valu
 hipError_t launch_early_stop(const Problem& pb, const cd* theta, const cd* h,
                              int32_t* done, int32_t* iters_done, int it, hipStream_t s);
 
+// Gaussian-approximation comparator EM (approx.hip, sbce_approx_em): one launch per call
+struct ApproxArgs {
+    const cd* yd;      // [B][Td][M]
+    const cd* yp;      // [B][Tp][M]
+    const cd* psid;    // [B][Td][N]
+    const cd* psip;    // [B][Tp][N]
+    const cd* xp;      // [B][Tp]
+    cd* g;             // [B][N][M] in: G_0, out: estimate
+    const double* varn_t;  // [B] or null
+    int32_t* status;   // [B] or null
+    int B, N, M, Tp, Td, iters;
+    double varn;
+    int status0;       // status word of a trial without a finding (0, or SBCE_STATUS_DEBUG)
+};
+bool approx_supported(int N, int M);
+hipError_t launch_approx(const ApproxArgs& a, hipStream_t s);
+
 }  // namespace sbce

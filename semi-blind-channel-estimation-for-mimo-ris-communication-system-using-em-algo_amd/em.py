@@ -23,6 +23,10 @@ Reference operator -> entry point here:
   EM_Gaussian_proposed(y_d, y_p, T_d, T_p, z_p, PsiTilde_td, varn, itera, H_initial, varx, n_tx)
                                MIMO_Gaussian_proposed.py:56-89 (Gaussian prior)
                                                                         -> EM_Gaussian_proposed()
+  EM_approx(PsiTilde_tp, PsiTilde_td, x_p, Y_p, Y_d, Iterations, varn, G)
+                               "Comparision/Comparision T_d vs NMSE.py":106-145 (semi-blind
+                               Gaussian approximation, the comparator)   -> EM_approx()
+                               batched: ``em_approx_batch`` (one sbce_approx_em call)
 Batched form for sweeps / benchmark: ``em_batch`` (one sbce_em call for all trials).
 
 Semantics kept from the reference: inputs are not mutated, theta is returned
@@ -441,6 +445,73 @@ def EM_Gaussian_proposed(y_d, y_p, T_d, T_p, z_p, PsiTilde_td, varn, itera, H_in
         print(np.linalg.norm(H))
     torch.cuda.current_stream().synchronize()
     return H
+
+
+def em_approx_batch(y_d, y_p, psi_d, psi_p, x_p, varn, updates, g0, return_device=False):
+    """``updates`` updates of the semi-blind Gaussian-approximation EM (the comparator EM_approx
+    of "Comparision/Comparision T_d vs NMSE.py":106-145) on a batch of independent trials: ONE
+    sbce_approx_em call, which is one kernel launch (csrc/approx.hip).
+
+    Layouts (complex128, batch-major, include/sbce.h): y_d (B,T_d,n_rx), y_p (B,T_p,n_rx),
+    psi_d (B,T_d,N), psi_p (B,T_p,N), x_p (B,T_p), g0 (B,N,n_rx) = the initial value G_0
+    (signal_model.initial_g_approx).  N <= 64, n_rx <= 8.  varn: one value or one per trial.
+    Inputs may be numpy arrays or CUDA complex128 tensors.  Returns dict(g (B,N,n_rx), status
+    (B,)): a trial whose normal matrix is singular (T_p + T_d < N) has SBCE_STATUS_SINGULAR set
+    and keeps its last finite iterate."""
+    torch = _torch()
+    lib = _lib.load()
+
+    def dev(x):
+        if isinstance(x, torch.Tensor):
+            return (x if x.is_cuda else x.to("cuda")).contiguous()
+        return _dev(torch, x, np.complex128)
+
+    Yd, Yp, Pd, Pp, Xp = dev(y_d), dev(y_p), dev(psi_d), dev(psi_p), dev(x_p)
+    G = dev(g0).clone()
+    B, T_d, n_rx = Yd.shape
+    T_p, N = Pp.shape[1], Pd.shape[2]
+    if (Yp.shape != (B, T_p, n_rx) or Pd.shape != (B, T_d, N) or Pp.shape != (B, T_p, N)
+            or Xp.reshape(B, -1).shape != (B, T_p) or G.shape != (B, N, n_rx)):
+        raise ValueError("em_approx_batch: inconsistent shapes")
+    varn0, Vt = _varn_arg(torch, varn, B)
+    dims = _lib.ApproxDims(B, N, n_rx, T_p, T_d, 0, varn0)
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.sbce_approx_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
+               "sbce_approx_workspace_bytes")
+    ws = torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+    status = torch.zeros(B, dtype=torch.int32, device="cuda")
+    ptrs = _lib.ApproxPtrs(Yd.data_ptr(), Yp.data_ptr(), Pd.data_ptr(), Pp.data_ptr(),
+                           Xp.data_ptr(), G.data_ptr(), Vt.data_ptr() if Vt is not None else None,
+                           status.data_ptr(), ws.data_ptr(), ws.numel())
+    _lib.check(lib.sbce_approx_em(dims, ptrs, int(updates),
+                                  torch.cuda.current_stream().cuda_stream), "sbce_approx_em")
+    out = dict(g=G, status=status)
+    if return_device:
+        return out
+    torch.cuda.current_stream().synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def EM_approx(PsiTilde_tp, PsiTilde_td, x_p, Y_p, Y_d, Iterations, varn, G=None, verbose=False):
+    """Semi-blind Gaussian-approximation EM with the reference's signature and layouts
+    ("Comparision/Comparision T_d vs NMSE.py":106-145): PsiTilde_tp N x L_p, PsiTilde_td N x L_d,
+    x_p (L_p, 1), Y_p M x L_p, Y_d M x L_d.  G_0 is computed on the host (:107-108), the device
+    runs Iterations + 1 updates (``while i <= Iterations``, :114) and the N x M estimate is
+    returned.  ``G`` is accepted and unused, as in the reference, which only prints its norm."""
+    from .signal_model import initial_g_approx
+    global last_status
+    Pp, Pd = np.asarray(PsiTilde_tp, dtype=complex), np.asarray(PsiTilde_td, dtype=complex)
+    Yp, Yd = np.asarray(Y_p, dtype=complex), np.asarray(Y_d, dtype=complex)
+    xp = np.asarray(x_p, dtype=complex).reshape(-1)
+    G0 = initial_g_approx(Pp, xp, Yp)
+    if verbose and G is not None:
+        print("original G", np.linalg.norm(G))
+    res = em_approx_batch(Yd.T[None], Yp.T[None], Pd.T[None], Pp.T[None], xp[None], varn,
+                          int(Iterations) + 1, G0[None])
+    last_status = int(res["status"][0])
+    if verbose:
+        print("G_Cap", np.linalg.norm(res["g"][0]))
+    return res["g"][0]
 
 
 def ser_batch(x_dest, x_d_true):

@@ -190,6 +190,62 @@ def gaussian_symbols(n_tx, T, varx, rs=None):
     return rs.normal(loc=0, scale=np.sqrt(varx / 2), size=(n_tx, T * 2)).view(np.complex128)
 
 
+def channel_matrix1(varh, N, M, n_r=1, rs=None):
+    """channelMatrix1 of "Comparision/Comparision T_d vs NMSE.py":11-19 (the T_p script's is the
+    same): (h (N, n_r), F_H (M, N), G = diag(conj h) F_H^H (N, M), h_proposed), with h_proposed
+    the script's own row-major ``khatri_rao(h^T, F_H).flatten()``: entry [(a M + m) N + n] =
+    h[n, a] F_H[m, n].  G needs n_r = 1 (diagflat of one column), as in the scripts."""
+    rs = _rs(rs)
+    h = rs.normal(loc=0, scale=np.sqrt(varh / 2), size=(N, n_r * 2)).view(np.complex128)
+    F_H = rs.normal(loc=0, scale=np.sqrt(varh / 2), size=(M, N * 2)).view(np.complex128)
+    G = np.matmul(np.diagflat(np.conjugate(h).T), np.conjugate(F_H).T)
+    c = h.T[:, np.newaxis, :] * F_H[np.newaxis, :, :]
+    return h, F_H, G, c.reshape((-1,) + c.shape[2:]).flatten()
+
+
+def irs_matrix_nodirect(T_p, T_d, N, beta_min=0.0, beta_max=2 * np.pi, amp=1.0, rs=None):
+    """irsMatrix of the comparison scripts (T_d script :147-163): N x T_p DFT pilot phases over
+    N and N x T_d uniform data phases; no direct-path row is inserted anywhere."""
+    Ptp, Ptd = irs_matrix(T_p, T_d, N, beta_min, beta_max, amp, pilot="dft_n", rs=rs)
+    return Ptp[:N], Ptd
+
+
+def noise_approx(varn, M, L_p, L_d, rs=None):
+    """noise_approx of the comparison scripts (T_d script :184-187): (z_p (M, L_p), z_d (M, L_d)),
+    one normal draw each."""
+    rs = _rs(rs)
+    z_p = rs.normal(loc=0, scale=np.sqrt(varn / 2), size=(M, L_p * 2)).view(np.complex128)
+    z_d = rs.normal(loc=0, scale=np.sqrt(varn / 2), size=(M, L_d * 2)).view(np.complex128)
+    return z_p, z_d
+
+
+def received_approx(h, F_H, Psi_tp, Psi_td, x_d, x_p, z_p, z_d):
+    """received_approx of the comparison scripts (T_d script :190-201): y_t = F_H diag(psi_t) h
+    x_t + z_t per symbol, with the script's own products (bitwise replay).  Returns (Y_p (M, L_p),
+    Y_d (M, L_d))."""
+    def col(Psi, x, z, t):
+        return np.matmul(np.matmul(F_H, np.diagflat(Psi[:, t])), h) * x[t] + z[:, t][:, np.newaxis]
+    Y_p = np.column_stack([col(Psi_tp, x_p, z_p, t) for t in range(z_p.shape[1])])
+    Y_d = np.column_stack([col(Psi_td, x_d, z_d, t) for t in range(z_d.shape[1])])
+    return Y_p, Y_d
+
+
+def initial_g_approx(Psi_tp, x_p, Y_p):
+    """G_0 = conj(Y_p pinv(Psi_p diag(x_p)))^T of EM_approx (T_d script :107-108), N x M."""
+    S_p = np.matmul(Psi_tp, np.diagflat(x_p))
+    return np.conjugate(np.matmul(Y_p, np.linalg.pinv(S_p))).T
+
+
+def initial_estimate_per_pilot(U_p, Y_p, n_rx):
+    """The comparison scripts' h_initial (T_d script :181): ``np.linalg.pinv`` of the LIST Z_p is
+    a batched pseudo-inverse, so h_initial is (T_p, K, 1) with theta_p = pinv(Z_p[p]) y_p =
+    (conj(u_p) / ||u_p||^2) (x) y_p.  Returns the (T_p, K) stack."""
+    U = np.asarray(U_p)
+    Y = np.asarray(Y_p)
+    w = np.conj(U) / np.sum(np.abs(U) ** 2, axis=1, keepdims=True)
+    return np.einsum("pl,pr->plr", w, Y).reshape(U.shape[0], -1)
+
+
 def snr_to_varn(snr_db, power=10.0):
     """varn = power / 10^(SNR/10) (PMd/SNR/all_Detectors.py:351-354; power = 16-QAM E_s)."""
     return power / np.power(10.0, np.asarray(snr_db, dtype=float) / 10.0)

@@ -11,6 +11,12 @@ estimator with every trial of a sweep point batched into ONE sbce_em call.
   nmse_grid_detectors      "Proposed method/all_detectorsvsTd.py":345-405 (five EMs per T_d
                            point), extended over an SNR axis (BASELINE configs[4])
   llf_vs_iteration         "Proposed method/IterationsvsLLF.py":119-157 (LLF per EM iteration)
+  comparison_vs_td         "Comparision/Comparision T_d vs NMSE.py":203-253 and
+  comparison_vs_tp         "Comparision/Comparision T_p .py":171-222: the proposed exact EM beside
+                           the semi-blind Gaussian-approximation EM (EM_approx), the figure
+                           "Comparison between proposed method and the semi-blind Gaussian
+                           method"; per point one sbce_approx_em call over every trial (one kernel
+                           launch, csrc/approx.hip) and the proposed leg's sbce_em calls
 
 Data generation (host, NumPy):
   replay=True   the reference's exact legacy-RandomState call order after
@@ -25,7 +31,8 @@ import numpy as np
 
 from . import signal_model as sm
 from .distributed import Accumulators, shard
-from .em import em_batch, ser_batch, gauss_expand_batch, nmse_batch, _GAUSS_CONS
+from .em import (em_batch, em_approx_batch, ser_batch, gauss_expand_batch, nmse_batch,
+                 _GAUSS_CONS)
 from .qam import qam_constellation
 
 
@@ -532,3 +539,117 @@ def llf_vs_iteration(T_d=50, T_p=4, N=32, n_rx=2, n_tx=2, itera=5, monte_iter=3,
         acc.add(0, _nmse(r["theta"], b["h"]), llf_values=r["llf"])
     acc.allreduce(dist)
     return np.arange(itera), acc.mean_llf()[0], float(acc.mean_nmse()[0])
+
+
+def gen_comparison(axis, points, fixed, N=32, n_rx=8, monte_iter=1, M=4, varn=0.1, seed=0,
+                   replay=True, varh=1.0, keep=None):
+    """Data of the two comparison scripts in their draw orders (n_tx = 1, no direct path).
+    axis='td' ("Comparision/Comparision T_d vs NMSE.py":228-242, T_p = fixed): per trial
+    channelMatrix1, pilotSymbols(T_p); per point irsMatrix, symbols, received_proposed's noise,
+    noise_approx.  axis='tp' ("Comparision/Comparision T_p .py":196-211, T_d = fixed): per trial
+    channelMatrix1, symbols(T_d); per point irsMatrix, pilotSymbols, received_proposed,
+    noise_approx.  Returns points[k] = list of per-trial dicts holding both legs' inputs."""
+    if axis not in ("td", "tp"):
+        raise ValueError(axis)
+    keep = set(range(monte_iter)) if keep is None else set(keep)
+    out = [[] for _ in points]
+    if replay:
+        np.random.seed(seed)
+    for i in range(monte_iter):
+        rs = None if replay else _trial_rng(seed, i)
+        if not replay and i not in keep:
+            continue
+        h, F_H, G, h_prop = sm.channel_matrix1(varh, N, n_rx, 1, rs=rs)
+        if axis == "td":
+            X_p = sm.pilot_symbols(1, M, fixed, rs=rs)
+        else:
+            X_d, _ = sm.symbols(1, M, fixed, rs=rs)
+        for k, pt in enumerate(points):
+            tp, td = (fixed, pt) if axis == "td" else (pt, fixed)
+            Ptp, Ptd = sm.irs_matrix_nodirect(tp, td, N, rs=rs)
+            if axis == "td":
+                X_d, _ = sm.symbols(1, M, td, rs=rs)
+            else:
+                X_p = sm.pilot_symbols(1, M, tp, rs=rs)
+            x_p, x_d = np.vstack(X_p), np.vstack(X_d)
+            Y_p, Y_d, U_p, _, _ = sm.received_signals(tp, td, Ptp, Ptd, n_rx, 1, X_d, X_p, h_prop,
+                                                      varn, rs=rs, with_initial=False)
+            z_p, z_d = sm.noise_approx(varn, n_rx, tp, td, rs=rs)
+            Y_p_a, Y_d_a = sm.received_approx(h, F_H, Ptp, Ptd, x_d, x_p, z_p, z_d)
+            if i in keep:
+                out[k].append(dict(Y_d=Y_d, Y_p=Y_p, Psi_d=Ptd, Psi_p=Ptp, U_p=U_p, h=h_prop,
+                                   x_p=x_p.reshape(-1), Y_p_a=Y_p_a, Y_d_a=Y_d_a, G=G,
+                                   G0=sm.initial_g_approx(Ptp, x_p, Y_p_a)))
+    return out
+
+
+def _comparison(axis, points, fixed, N, n_rx, itera, monte_iter, M, varn, seed, replay, varh):
+    dist, world, rank = _dist()
+    mine = shard(monte_iter, world, rank).tolist()
+    data = gen_comparison(axis, points, fixed, N, n_rx, monte_iter, M, varn, seed, replay, varh,
+                          keep=mine)
+    cons = qam_constellation(M)
+    npt = len(points)
+    acc = Accumulators(2 * npt)                       # proposed points, then approximation points
+    for k, trials in enumerate(data):
+        if not trials:
+            continue
+        B = len(trials)
+        tp = trials[0]["Y_p"].shape[0]
+        y_d = np.stack([t["Y_d"] for t in trials])
+        y_p = np.stack([t["Y_p"] for t in trials])
+        psi_d = np.stack([t["Psi_d"].T for t in trials])
+        u_p = np.stack([t["U_p"] for t in trials])
+        h = np.stack([t["h"] for t in trials])
+        if M == 4:
+            # the scripts' per-pilot h_initial (signal_model.initial_estimate_per_pilot): the first
+            # E-step's distance sum_p ||y - Z_j theta_p||^2 is, for n_tx = 1 and the constant-modulus
+            # 4-QAM, the ordinary one at mean_p theta_p with noise parameter varn / sqrt(T_p)
+            th0 = np.stack([sm.initial_estimate_per_pilot(t["U_p"], t["Y_p"], n_rx).mean(axis=0)
+                            for t in trials])
+            r = em_batch(y_d, y_p, psi_d, u_p, cons, varn / np.sqrt(tp), 1, th0, mode="soft",
+                         return_device=itera > 1)
+            if itera > 1:
+                r = em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera - 1, r["theta"], mode="soft")
+        else:
+            th0 = np.stack([sm.initial_estimate(t["U_p"], t["Y_p"], n_rx) for t in trials])
+            r = em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, th0, mode="soft")
+        acc.add(k, _nmse(r["theta"], h))
+        ra = em_approx_batch(np.stack([t["Y_d_a"].T for t in trials]),
+                             np.stack([t["Y_p_a"].T for t in trials]), psi_d,
+                             np.stack([t["Psi_p"].T for t in trials]),
+                             np.stack([t["x_p"] for t in trials]), varn, itera + 1,
+                             np.stack([t["G0"] for t in trials]), return_device=True)
+        Gt = np.stack([t["G"] for t in trials]).reshape(B, -1)
+        acc.add(npt + k, nmse_batch(ra["g"].reshape(B, -1), Gt).cpu().numpy())
+    acc.allreduce(dist)
+    mean = acc.mean_nmse()
+    return np.asarray(points), {"proposed": mean[:npt], "approx": mean[npt:]}
+
+
+def comparison_vs_td(T_d=(20, 30, 40, 50, 60, 70, 80, 90, 100), T_p=16, N=32, n_rx=8, itera=20,
+                     monte_iter=1, M=4, varn=0.1, seed=0, replay=True, varh=1.0):
+    """Mean NMSE per data length of the proposed exact EM and of the semi-blind Gaussian
+    approximation EM ("Comparision/Comparision T_d vs NMSE.py":203-253; n_tx = 1, no direct
+    path).  Returns (T_d, {"proposed": curve, "approx": curve}).
+
+    Approximation leg: G_0 on the host, then ONE sbce_approx_em call per point over every trial
+    with itera + 1 updates (`while i <= Iterations`, :114); NMSE = ||G_hat - G||_F^2 / ||G||_F^2
+    (:248, trace(abs(E^H E)) / ||G||^2) by sbce_nmse.
+    Proposed leg: the exact-soft sbce_em path.  The scripts' h_initial is a per-pilot stack
+    (np.linalg.pinv of the LIST Z_p, :181); with M = 4 (constant modulus) and n_tx = 1 that start
+    is replayed exactly by two calls -- one iteration at varn / sqrt(T_p) from the mean of the
+    per-pilot estimates, then itera - 1 iterations at varn.  For any other M the package's usual
+    stacked pseudo-inverse start (signal_model.initial_estimate) is used instead, which is NOT the
+    scripts' start."""
+    return _comparison("td", tuple(T_d), T_p, N, n_rx, itera, monte_iter, M, varn, seed, replay,
+                       varh)
+
+
+def comparison_vs_tp(T_p=(4, 8, 12, 16, 20, 24, 28, 32, 36, 40), T_d=50, N=32, n_rx=8, itera=15,
+                     monte_iter=50, M=4, varn=0.1, seed=0, replay=True, varh=1.0):
+    """Mean NMSE per pilot length of the proposed exact EM and of the semi-blind Gaussian
+    approximation EM ("Comparision/Comparision T_p .py":171-222); legs, initial values and
+    return value as comparison_vs_td."""
+    return _comparison("tp", tuple(T_p), T_d, N, n_rx, itera, monte_iter, M, varn, seed, replay,
+                       varh)
