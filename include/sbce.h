@@ -273,6 +273,73 @@ int sbce_approx_workspace_bytes(const sbce_approx_dims* d, size_t* bytes);
 int sbce_approx_em(const sbce_approx_dims* d, const sbce_approx_ptrs* p, int iters,
                    void* hip_stream);
 
+/* ---- Batched data detector and soft demapper (an additive extension of ABI 7: no existing
+ * struct or entry point changes, so the version number stays): decisions, symbol posteriors and bit
+ * L-values of every data symbol of a batch from a GIVEN channel estimate theta (any estimator's
+ * output, the pilot-only start, or the true channel).  Per (trial b, data symbol t) the effective
+ * channel is H_t[r][a] = sum_p psi_d[b][t][p] theta[b][(p n_tx + a) n_rx + r] (the E-step's
+ * layout); over the J = M^n_tx hypotheses x_j in itertools.product order (first stream slowest)
+ * with d_j = ||y_t - H_t x_j||^2 and s2 the posterior denominator:
+ *   x_hat, idx_hat  joint decision argmin_j d_j, ties to the lowest j (np.argmin)
+ *   post[a][s]      sum_{j: x_j[a] = cons[s]} e^{-d_j/s2} / sum_j e^{-d_j/s2}
+ *   llr[a][i]       log sum_{bit_i = 0} e^{-d_j/s2} - log sum_{bit_i = 1} e^{-d_j/s2}, with
+ *                   bit_i(s) = (labels[s] >> i) & 1, i < log2 M: the L-value log(p0 / p1) of
+ *                   "Proposed method/QAM.py":164-185 (bits LSB-first, :8-11) on the MIMO
+ *                   posterior; with SBCE_DETECT_MAXLOG (min_{bit_i = 1} d_j - min_{bit_i = 0} d_j) / s2
+ *   err[b]          {symbol entries with idx_hat != the table index nearest x_d_true, differing
+ *                   label bits} of trial b (integer adds)
+ * All sums are formed in the log domain (per-class minimum shifts), so every output is finite
+ * for any s2 > 0.  cons is ANY table of M complex points and labels any permutation of 0..M-1:
+ * no grid structure is assumed.  Results of a trial do not depend on the batch around it.
+ * sbce_dims / sbce_ptrs are not used.  Batch-major layouts (complex128 unless noted):
+ *   y_d      [B][T_d][n_rx]            psi_d  [B][T_d][P]       cons  [M]      theta [B][K]
+ *   labels   [M] int32                 sigma2_t [B] float64     x_d_true [B][T_d][n_tx]
+ *   x_hat    [B][T_d][n_tx]            idx_hat [B][T_d][n_tx] int32
+ *   post     [B][T_d][n_tx][M] float64 llr    [B][T_d][n_tx][log2 M] float64
+ *   err      [B][2] int32 */
+#define SBCE_DETECT_MAXLOG 1    /* sbce_detect_dims.flags bit 0: max-log L-values in `llr` */
+
+typedef struct sbce_detect_dims {
+    int32_t batch;      /* B: independent trials (>= 1) */
+    int32_t n_tx;       /* streams (1..4) */
+    int32_t n_rx;       /* receive antennas (1..8) */
+    int32_t n_psi;      /* P = rows of PsiTilde_td (>= 1) */
+    int32_t t_d;        /* data symbols (>= 1) */
+    int32_t m;          /* table size (power of two, 2..64), J = m^n_tx <= 65536 */
+    int32_t flags;      /* SBCE_DETECT_*; every other bit 0 */
+    double sigma2;      /* the posterior denominator itself (> 0): varn^2 for the EM posterior
+                           (Proposed_method_NMSEvsTp.py:66), varn for the noise the data carry */
+} sbce_detect_dims;
+
+typedef struct sbce_detect_ptrs {
+    const void* y_d;
+    const void* psi_d;
+    const void* cons;
+    const void* theta;
+    const int32_t* labels;   /* may be NULL unless llr or err is set */
+    const double* sigma2_t;  /* may be NULL: [B] per-trial sigma2 (values > 0), as sbce_ptrs.varn_t */
+    const void* x_d_true;    /* may be NULL unless err is set */
+    void* x_hat;             /* may be NULL */
+    int32_t* idx_hat;        /* may be NULL */
+    double* post;            /* may be NULL */
+    double* llr;             /* may be NULL (requires labels) */
+    int32_t* err;            /* may be NULL (requires x_d_true and labels); zeroed by the call */
+    void* workspace;         /* may be NULL when sbce_detect_workspace_bytes reports 0 */
+    size_t workspace_bytes;
+} sbce_detect_ptrs;
+
+/* Device workspace of sbce_detect for `d` (0 in this version: a symbol's state lives in LDS and
+ * registers). */
+int sbce_detect_workspace_bytes(const sbce_detect_dims* d, size_t* bytes);
+
+/* One detection pass over every (trial, data symbol): one memset of `err` (when set) and one
+ * kernel launch on `hip_stream`, no allocation, no synchronisation; capturable in a HIP graph.
+ * Decided before any HIP call -- SBCE_EINVAL: null dims / ptrs / required pointer, batch, t_d,
+ * n_psi, n_tx or n_rx < 1, m not a power of two in 2..64, sigma2 <= 0, llr without labels, err
+ * without x_d_true or labels, unknown flag bits, a misaligned pointer (16 bytes complex, 8 float64,
+ * 4 int32); SBCE_EUNSUPPORTED: n_tx > 4, n_rx > 8 or m^n_tx > 65536; SBCE_EWORKSPACE. */
+int sbce_detect(const sbce_detect_dims* d, const sbce_detect_ptrs* p, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

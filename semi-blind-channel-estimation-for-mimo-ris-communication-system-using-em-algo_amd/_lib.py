@@ -31,11 +31,13 @@ SBCE_STATUS_DETECTOR = 4
 SBCE_STATUS_DEBUG = 8
 SBCE_STATUS_RANK = 16
 SBCE_STATUS_SINGULAR = 32
+SBCE_DETECT_MAXLOG = 1
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_workspace_bytes_solve", "sbce_em",
             "sbce_estep", "sbce_mstep", "sbce_ser", "sbce_gauss_expand", "sbce_nmse",
-            "sbce_approx_workspace_bytes", "sbce_approx_em")
+            "sbce_approx_workspace_bytes", "sbce_approx_em",
+            "sbce_detect_workspace_bytes", "sbce_detect")
 
 
 class SbceUnavailable(RuntimeError):
@@ -75,6 +77,22 @@ class ApproxPtrs(ctypes.Structure):
                 ("psi_p", ctypes.c_void_p), ("x_p", ctypes.c_void_p), ("g", ctypes.c_void_p),
                 ("varn_t", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class DetectDims(ctypes.Structure):
+    """sbce_detect_dims (include/sbce.h): the batched data detector / soft demapper."""
+    _fields_ = [("batch", ctypes.c_int32), ("n_tx", ctypes.c_int32), ("n_rx", ctypes.c_int32),
+                ("n_psi", ctypes.c_int32), ("t_d", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("sigma2", ctypes.c_double)]
+
+
+class DetectPtrs(ctypes.Structure):
+    _fields_ = [("y_d", ctypes.c_void_p), ("psi_d", ctypes.c_void_p), ("cons", ctypes.c_void_p),
+                ("theta", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+                ("sigma2_t", ctypes.c_void_p), ("x_d_true", ctypes.c_void_p),
+                ("x_hat", ctypes.c_void_p), ("idx_hat", ctypes.c_void_p), ("post", ctypes.c_void_p),
+                ("llr", ctypes.c_void_p), ("err", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_size_t)]
 
 
 _lib = None
@@ -134,6 +152,12 @@ def load(path=None):
     lib.sbce_approx_em.restype = ctypes.c_int
     lib.sbce_approx_em.argtypes = [ctypes.POINTER(ApproxDims), ctypes.POINTER(ApproxPtrs),
                                    ctypes.c_int, ctypes.c_void_p]
+    lib.sbce_detect_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_detect_workspace_bytes.argtypes = [ctypes.POINTER(DetectDims),
+                                                ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_detect.restype = ctypes.c_int
+    lib.sbce_detect.argtypes = [ctypes.POINTER(DetectDims), ctypes.POINTER(DetectPtrs),
+                                ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

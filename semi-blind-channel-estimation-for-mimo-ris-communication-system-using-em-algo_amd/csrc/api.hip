@@ -599,4 +599,45 @@ int sbce_approx_em(const sbce_approx_dims* d, const sbce_approx_ptrs* p, int ite
     return hip_rc(launch_approx(a, (hipStream_t)hip_stream));
 }
 
+int sbce_detect_workspace_bytes(const sbce_detect_dims* d, size_t* bytes) {
+    if (!d || !bytes) return SBCE_EINVAL;
+    *bytes = 0;                          // a symbol's state lives in LDS and registers
+    return SBCE_OK;
+}
+
+int sbce_detect(const sbce_detect_dims* d, const sbce_detect_ptrs* p, void* hip_stream) {
+    if (!d || !p) return SBCE_EINVAL;
+    if (d->batch < 1 || d->n_tx < 1 || d->n_rx < 1 || d->n_psi < 1 || d->t_d < 1 ||
+        !(d->sigma2 > 0.0) || (d->flags & ~SBCE_DETECT_MAXLOG))
+        return SBCE_EINVAL;
+    int lgm = 0;
+    while ((1 << lgm) < d->m) ++lgm;
+    if (d->m < 2 || d->m > 64 || (1 << lgm) != d->m) return SBCE_EINVAL;
+    const void* req[] = {p->y_d, p->psi_d, p->cons, p->theta};
+    for (const void* q : req)
+        if (!q || !aligned16(q)) return SBCE_EINVAL;
+    if ((p->llr || p->err) && !p->labels) return SBCE_EINVAL;
+    if (p->err && !p->x_d_true) return SBCE_EINVAL;
+    if (!aligned16(p->x_d_true) || !aligned16(p->x_hat)) return SBCE_EINVAL;
+    if (((uintptr_t)p->sigma2_t & 7) || ((uintptr_t)p->post & 7) || ((uintptr_t)p->llr & 7))
+        return SBCE_EINVAL;
+    if (((uintptr_t)p->labels & 3) || ((uintptr_t)p->idx_hat & 3) || ((uintptr_t)p->err & 3))
+        return SBCE_EINVAL;
+    if (!detect_supported(d->n_tx, d->n_rx, d->m)) return SBCE_EUNSUPPORTED;
+    size_t need = 0;
+    sbce_detect_workspace_bytes(d, &need);
+    if (need && (!p->workspace || !aligned16(p->workspace))) return SBCE_EINVAL;
+    if (p->workspace_bytes < need) return SBCE_EWORKSPACE;
+    clear_stale_error();
+    DetectArgs a;
+    a.yd = (const cd*)p->y_d; a.psid = (const cd*)p->psi_d; a.cons = (const cd*)p->cons;
+    a.theta = (const cd*)p->theta; a.labels = p->labels; a.sigma2_t = p->sigma2_t;
+    a.xd = (const cd*)p->x_d_true; a.xhat = (cd*)p->x_hat; a.idx = p->idx_hat; a.post = p->post;
+    a.llr = p->llr; a.err = p->err;
+    a.B = d->batch; a.NT = d->n_tx; a.NR = d->n_rx; a.P = d->n_psi; a.Td = d->t_d; a.M = d->m;
+    a.lgM = lgm; a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0; a.TC = 0; a.chunks = 0;
+    a.sigma2 = d->sigma2;
+    return hip_rc(launch_detect(a, (hipStream_t)hip_stream));
+}
+
 }  // extern "C"

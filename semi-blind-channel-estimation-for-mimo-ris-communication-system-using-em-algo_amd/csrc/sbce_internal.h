@@ -505,4 +505,27 @@ struct ApproxArgs {
 bool approx_supported(int N, int M);
 hipError_t launch_approx(const ApproxArgs& a, hipStream_t s);
 
+// Batched data detector / soft demapper (detect.hip, sbce_detect): one launch per call
+struct DetectArgs {
+    const cd* yd;      // [B][Td][NR]
+    const cd* psid;    // [B][Td][P]
+    const cd* cons;    // [M]
+    const cd* theta;   // [B][P*NT*NR]
+    const int32_t* labels;    // [M] or null
+    const double* sigma2_t;   // [B] or null
+    const cd* xd;      // [B][Td][NT] or null
+    cd* xhat;          // [B][Td][NT] or null
+    int32_t* idx;      // [B][Td][NT] or null
+    double* post;      // [B][Td][NT][M] or null
+    double* llr;       // [B][Td][NT][lgM] or null
+    int32_t* err;      // [B][2] or null (zeroed before the launch)
+    int B, NT, NR, P, Td, M, lgM;
+    int maxlog;        // llr holds the max-log L-values
+    int TC, chunks;    // symbols per workgroup, workgroups per trial (set by launch_detect)
+    double sigma2;
+};
+constexpr int kDetectMaxJ = 65536;
+bool detect_supported(int NT, int NR, int M);   // 1..4, 1..8, M^NT <= kDetectMaxJ
+hipError_t launch_detect(DetectArgs a, hipStream_t s);
+
 }  // namespace sbce

@@ -514,6 +514,131 @@ def EM_approx(PsiTilde_tp, PsiTilde_td, x_p, Y_p, Y_d, Iterations, varn, G=None,
     return res["g"][0]
 
 
+_WANT = ("x_hat", "idx", "llr", "post")
+
+
+def _detect_labels(cons_size, labels, need):
+    """The labelling of a detect call: the given permutation, or the reference modem's Gray
+    labelling when the table has a square-QAM size; None when none is needed or known."""
+    from .qam import gray_labeling
+    if labels is not None:
+        lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        if lab.size != cons_size or not np.array_equal(np.sort(lab), np.arange(cons_size)):
+            raise ValueError("labels must be a permutation of 0..M-1")
+        return lab
+    L = int(round(np.sqrt(cons_size)))
+    if L * L == cons_size and not L & (L - 1):
+        return gray_labeling(cons_size)
+    if need:
+        raise ValueError("this table has no default labelling: pass labels= for LLRs / bit errors")
+    return None
+
+
+def _detect_call(torch, Yd, Ps, Cs, Th, n_tx, sigma2, sigma2_t, lab, Xd, maxlog, want):
+    """One sbce_detect on device tensors; returns the dict of device outputs."""
+    lib = _lib.load()
+    B, T_d, n_rx = Yd.shape
+    P, M = Ps.shape[2], Cs.shape[0]
+    if Ps.shape != (B, T_d, P) or Th.shape != (B, P * n_tx * n_rx):
+        raise ValueError("detect: inconsistent shapes")
+    lgM = max(int(M - 1).bit_length(), 1)
+    bad = set(want) - set(_WANT)
+    if bad:
+        raise ValueError(f"unknown outputs {sorted(bad)}")
+    out = {}
+    if "x_hat" in want:
+        out["x_hat"] = torch.empty((B, T_d, n_tx), dtype=torch.complex128, device="cuda")
+    if "idx" in want:
+        out["idx"] = torch.empty((B, T_d, n_tx), dtype=torch.int32, device="cuda")
+    if "post" in want:
+        out["post"] = torch.empty((B, T_d, n_tx, M), dtype=torch.float64, device="cuda")
+    if "llr" in want:
+        out["llr"] = torch.empty((B, T_d, n_tx, lgM), dtype=torch.float64, device="cuda")
+    if Xd is not None and lab is not None:
+        out["err"] = torch.empty((B, 2), dtype=torch.int32, device="cuda")
+
+    def ptr(k):
+        return out[k].data_ptr() if k in out else None
+
+    dims = _lib.DetectDims(B, n_tx, n_rx, P, T_d, M, _lib.SBCE_DETECT_MAXLOG if maxlog else 0,
+                           float(sigma2))
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.sbce_detect_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
+               "sbce_detect_workspace_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device="cuda") if nb.value else None
+    ptrs = _lib.DetectPtrs(Yd.data_ptr(), Ps.data_ptr(), Cs.data_ptr(), Th.data_ptr(),
+                           lab.data_ptr() if lab is not None else None,
+                           sigma2_t.data_ptr() if sigma2_t is not None else None,
+                           Xd.data_ptr() if Xd is not None else None,
+                           ptr("x_hat"), ptr("idx"), ptr("post"), ptr("llr"), ptr("err"),
+                           ws.data_ptr() if ws is not None else None, nb.value)
+    _lib.check(lib.sbce_detect(dims, ptrs, torch.cuda.current_stream().cuda_stream), "sbce_detect")
+    return out
+
+
+def _sigma2_arg(torch, varn, B, noise):
+    """(dims.sigma2, per-trial device tensor or None): the posterior denominator, varn**2 for the
+    EM posterior (noise='em') or varn itself, the noise the data were drawn with (noise='true')."""
+    if noise not in ("em", "true"):
+        raise ValueError("noise must be 'em' or 'true'")
+    v0, Vt = _varn_arg(torch, varn, B)
+    if noise == "em":
+        return v0 * v0, (Vt * Vt if Vt is not None else None)
+    return v0, Vt
+
+
+def detect_batch(y_d, psi_d, cons, theta, varn, n_tx, labels=None, x_d_true=None, noise="em",
+                 maxlog=False, want=_WANT, return_device=False):
+    """Decide the data symbols of a batch of trials from a channel estimate and say how good the
+    decisions are: ONE sbce_detect call (one kernel launch, csrc/detect.hip).
+
+    y_d (B,T_d,n_rx), psi_d (B,T_d,P), cons (M,) ANY table of M = 2..64 complex points, theta
+    (B,K) any estimate in the E-step's layout (em_batch's theta, h_initial, the true h); numpy
+    arrays or CUDA tensors.  varn: one value or (B,); noise='em' uses sigma^2 = varn**2 (the EM
+    posterior), noise='true' sigma^2 = varn.  labels: an int permutation of 0..M-1 (bit i of
+    symbol s = (labels[s] >> i) & 1); None means qam.gray_labeling for a square-QAM-sized table.
+    Returns a dict with the outputs named in ``want``: x_hat (B,T_d,n_tx) and idx (int32 table
+    indices) = the joint ML decision; post (B,T_d,n_tx,M) per-stream symbol posteriors; llr
+    (B,T_d,n_tx,log2 M) L-values log(p0/p1), exact or (maxlog=True) max-log; with x_d_true
+    also err (B,2) int32 = per-trial symbol and bit error counts."""
+    torch = _torch()
+
+    def dev(x):
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            return (x if x.is_cuda else x.to("cuda")).contiguous()
+        return _dev(torch, x, np.complex128)
+
+    Yd, Ps, Cs, Th, Xd = dev(y_d), dev(psi_d), dev(cons), dev(theta), dev(x_d_true)
+    lab = _detect_labels(Cs.shape[0], labels, "llr" in want or Xd is not None)
+    lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
+    s2, s2t = _sigma2_arg(torch, varn, Yd.shape[0], noise)
+    out = _detect_call(torch, Yd, Ps, Cs, Th, int(n_tx), s2, s2t, lab_d, Xd, maxlog, tuple(want))
+    if return_device:
+        return out
+    torch.cuda.current_stream().synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def detect(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, labels=None, X_d=None,
+           noise="em", maxlog=False, want=_WANT):
+    """detect_batch for one trial in the reference's list layouts (as em()): Y_d a list of
+    (n_rx,1) observations, PsiTilde_td (N+1) x T_d, all_possibleSymbols the (M^n_tx, n_tx)
+    hypothesis table, theta (K,1); X_d an optional list of true symbol vectors (error counts).
+    Returns the dict of detect_batch without the batch axis."""
+    aps = np.asarray(all_possibleSymbols)
+    n_tx = aps.shape[1]
+    cons = cons_from_aps(aps, int(M))
+    T_d = len(Y_d)
+    y = np.stack([np.asarray(v).reshape(-1) for v in Y_d])[None]
+    psi = np.asarray(PsiTilde_td)[:, :T_d].T[None]
+    xt = None if X_d is None else np.stack([np.asarray(x).reshape(-1) for x in X_d[:T_d]])[None]
+    r = detect_batch(y, psi, cons, np.asarray(theta, dtype=complex).reshape(1, -1), varn, n_tx,
+                     labels=labels, x_d_true=xt, noise=noise, maxlog=maxlog, want=want)
+    return {k: v[0] for k, v in r.items()}
+
+
 def ser_batch(x_dest, x_d_true):
     """Per-trial SER on the device (sbce_ser): (ser_reference, ser_elementwise), the first
     being the expression of PMd/SER/log_max_SER.py:162."""
@@ -801,6 +926,31 @@ class EMEngine:
         rc = fn(ctypes.byref(self.dims), ctypes.byref(self.ptrs), ctypes.c_void_p(self.mom.data_ptr()),
                 int(phase), ctypes.c_void_p(self.torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "sbce_debug_mstep_phase")
+
+    def detect(self, labels=None, x_d_true=None, noise="em", maxlog=False, want=_WANT,
+               return_device=False):
+        """One sbce_detect on the engine's resident y_d, psi_d, cons and CURRENT theta (after
+        run(): the estimate; before: theta0), on the current stream: the outputs of detect_batch.
+        x_d_true defaults to the engine's own (error counters when it has one)."""
+        torch = self.torch
+        xd = self.x_d if x_d_true is None else (
+            x_d_true.to("cuda").contiguous() if isinstance(x_d_true, torch.Tensor)
+            else _dev(torch, x_d_true, np.complex128))
+        lab = _detect_labels(self.M, labels, "llr" in want or xd is not None)
+        lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
+        vt = self.varn_t
+        if noise == "em":
+            s2, s2t = self.varn * self.varn, (vt * vt if vt is not None else None)
+        elif noise == "true":
+            s2, s2t = self.varn, vt
+        else:
+            raise ValueError("noise must be 'em' or 'true'")
+        out = _detect_call(torch, self.y_d, self.psi_d, self.cons, self.theta, self.n_tx, s2, s2t,
+                           lab_d, xd, maxlog, tuple(want))
+        if return_device:
+            return out
+        torch.cuda.current_stream().synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     def nmse(self):
         """Per-trial NMSE of the current theta against h (device, sbce_nmse)."""

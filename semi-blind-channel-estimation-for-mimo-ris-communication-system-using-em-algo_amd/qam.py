@@ -24,6 +24,25 @@ def energy_per_symbol(M):
     return float(np.mean(c.real ** 2 + c.imag ** 2))
 
 
+def gray_labeling(M):
+    """The reference modem's default binary labelling of the square table above: 'reflected_2d'
+    ("Proposed method/QAM.py":211-217), label = gray(i_I) + L * gray(i_Q) for the point with
+    in-phase index i_I and quadrature index i_Q (table index s = i_I + L * i_Q)."""
+    L = int(round(np.sqrt(M)))
+    if L * L != M or L & (L - 1):
+        raise ValueError("M must be a square power of two (4, 16, 64, 256)")
+    g = np.arange(L, dtype=np.int64)
+    g ^= g >> 1
+    return (g[None, :] + L * g[:, None]).reshape(-1).astype(np.int32)
+
+
+def bits_of(labels):
+    """(M, log2 M) array of the labels' bits, LSB first (QAM.py:8-11, :31)."""
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    m = max(int(labels.size - 1).bit_length(), 1)
+    return ((labels[:, None] >> np.arange(m)[None, :]) & 1).astype(np.int8)
+
+
 def all_possible_symbols(cons, n_tx):
     """J = M^n_tx hypotheses in itertools.product order (first stream slowest)."""
     cons = np.asarray(cons)

@@ -6,6 +6,9 @@ estimator with every trial of a sweep point batched into ONE sbce_em call.
   nmse_vs_snr  "Proposed method/SNR/all_Detectors.py":331-395 (its five EMs: PM r=1, log-max,
                ZF, MMSE, exact)
   ser_vs_snr   "Proposed method/SER/log_max_SER.py":124-167 (log-max EM decisions)
+  detection_vs_snr  SER / BER / NMSE per SNR of ONE detector (sbce_detect) fed the channel of
+               every estimator, the pilot-only start and the true channel, on the data of
+               SNR/all_Detectors.py (gen_snr)
   nmse_vs_tp_superimposed  "Parallel/ParallelProtocol_Tp.py":106-136 (superimposed pilots)
   nmse_vs_tp_gaussian      "Proposed method/MIMO_Gaussian_proposed.py":158-177 (Gaussian prior)
   nmse_grid_detectors      "Proposed method/all_detectorsvsTd.py":345-405 (five EMs per T_d
@@ -32,8 +35,8 @@ import numpy as np
 from . import signal_model as sm
 from .distributed import Accumulators, shard
 from .em import (em_batch, em_approx_batch, ser_batch, gauss_expand_batch, nmse_batch,
-                 _GAUSS_CONS)
-from .qam import qam_constellation
+                 detect_batch, _GAUSS_CONS)
+from .qam import qam_constellation, gray_labeling
 
 
 def _dist():
@@ -307,6 +310,63 @@ def ser_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=20, N=30, n_rx=2, n_tx=2,
     acc.allreduce(dist)
     ser = acc.mean_extra()
     return np.asarray(SNR), ser[:, 0], ser[:, 1], acc.mean_nmse()
+
+
+# channel fed to the detector: the pilot-only start h0, the true channel, or em_batch's theta
+DETECT_ESTIMATORS = ("pilot", "soft", "hard", "pm", "zf", "mmse", "genie")
+
+
+def detection_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2, itera=5,
+                     monte_iter=15, M=4, estimators=DETECT_ESTIMATORS, power=10.0, seed=0,
+                     replay=True, varh=1.0, partition_r=1, noise="em", labels=None,
+                     batch_snr=True):
+    """Uncoded SER and BER (and NMSE) per SNR of the joint ML detector (sbce_detect) fed each
+    estimator's channel, on gen_snr's data (the layout of PMd/SNR/all_Detectors.py:362-370):
+    'pilot' = the pilot-only start h0, 'genie' = the true h, every other name an em_batch mode
+    whose theta after ``itera`` iterations is used.  The SAME detector serves every estimator;
+    per-trial symbol and bit error counts come from the device counters and are accumulated as
+    extras, all-reduced ONCE with the NMSE sums.  noise: the detector's sigma^2 ('em' varn^2,
+    'true' varn); labels: the bit labelling (default qam.gray_labeling).
+    Returns (SNR, ser {est: curve}, ber {est: curve}, nmse {est: curve})."""
+    estimators = tuple(estimators)
+    bad = [e for e in estimators if e not in ("pilot", "genie", "soft", "hard", "pm", "pm_soft",
+                                              "zf", "mmse")]
+    if bad:
+        raise ValueError(f"unknown estimators {bad}")
+    dist, world, rank = _dist()
+    mine = shard(monte_iter, world, rank).tolist()
+    points, varns = gen_snr(SNR, T_d, T_p, N, n_rx, n_tx, monte_iter, M, power, seed, replay,
+                            varh, keep=mine)
+    cons = qam_constellation(M)
+    lab = gray_labeling(M) if labels is None else np.asarray(labels, dtype=np.int32)
+    ne, ns = len(estimators), len(SNR)
+    acc = Accumulators(ne * ns, n_extra=2)
+    for ks, counts, b, vn in _snr_groups(points, varns, batch_snr):
+        x_true = np.stack([t["X_d"] for k in ks for t in points[k]])
+        off = np.cumsum([0] + counts)
+        for ei, est in enumerate(estimators):
+            if est == "pilot":
+                theta = b["theta0"]
+            elif est == "genie":
+                theta = b["h"]
+            else:
+                theta = em_batch(b["y_d"], b["y_p"], b["psi_d"], b["u_p"], cons, vn, itera,
+                                 b["theta0"], mode=est,
+                                 partition_r=partition_r if est.startswith("pm") else 0)["theta"]
+            r = detect_batch(b["y_d"], b["psi_d"], cons, theta, vn, n_tx, labels=lab,
+                             x_d_true=x_true, noise=noise, want=())
+            nm = _nmse(np.asarray(theta), b["h"])
+            for k, o0, o1 in zip(ks, off[:-1], off[1:]):
+                acc.add(ei * ns + k, nm[o0:o1], extra_values=r["err"][o0:o1])
+    acc.allreduce(dist)                   # the sweep's only collective
+    n_sym = np.maximum(acc.count, 1) * (T_d * n_tx)
+    lgM = max(int(M - 1).bit_length(), 1)
+    ser = (acc.extra[:, 0] / n_sym).reshape(ne, ns)
+    ber = (acc.extra[:, 1] / (n_sym * lgM)).reshape(ne, ns)
+    nmse = acc.mean_nmse().reshape(ne, ns)
+    return (np.asarray(SNR), {e: ser[i] for i, e in enumerate(estimators)},
+            {e: ber[i] for i, e in enumerate(estimators)},
+            {e: nmse[i] for i, e in enumerate(estimators)})
 
 
 def gen_superimposed(T_p=(4, 8, 12, 16, 20, 24, 28, 32, 36, 40), T_d=50, N=32, n_rx=8, n_tx=1,
