@@ -889,23 +889,56 @@ __device__ __forceinline__ void load_tile16(const cd* R, int L, int row0, int c0
     }
 }
 
-// TRSM of one 16-row tile (values in X, LDS) against the factored diagonal block of the
-// sub-panel at column c0 (inverse Di): L = C D^{-H}, written to R; y rows updated with the
-// sub-panel's y block yb.  Returns X[li][lk + 4q] in xv (the A-operand layout of k-step q).
+// The same tile in the MFMA operand layout ("transposed": lane (li, lk) holds row li, columns
+// lk + 4q), straight from R: what trsm_tile16 multiplies, and what the operand-exchanged
+// updates (csubT_step) accumulate in
+__device__ __forceinline__ void load_tileT(const cd* R, int L, int row0, int c0, int w, int li, int lk,
+                                           bool on, cd* v) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = lk + 4 * q;
+        v[q] = (on && row0 + li < L && c < w) ? R[(size_t)(row0 + li) * L + c0 + c] : czero();
+    }
+}
+
+// csub_step with the MFMA's operands exchanged: the accumulators hold the tile transposed
+// (lane (li, lk), value q = C[row li][column lk + 4q]), which is trsm_tile16's operand layout,
+// so an updated tile goes into the next TRSM without a trip through LDS.  v indexes C's rows
+// (lane li = row), t its columns (lane li = column); every entry is the same sum of the same
+// products in the same order as csub_step's (the signs sit on t, which is used once, so that
+// a v shared by two half tiles is held once: -(a b) = (-a) b = a (-b) exactly).
+template <bool G3>
+__device__ __forceinline__ void csubT_step(mf4& cre, mf4& cim, mf4& c2, cd v, cd t) {
+    if constexpr (G3) {
+        cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-t.x, v.x, cre, 0, 0, 0);
+        c2 = __builtin_amdgcn_mfma_f64_16x16x4f64(-t.y, v.y, c2, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f64_16x16x4f64(t.y - t.x, v.x + v.y, cim, 0, 0, 0);
+    } else {
+        cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-t.x, v.x, cre, 0, 0, 0);
+        cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-t.y, v.y, cre, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f64_16x16x4f64(-t.x, v.y, cim, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f64_16x16x4f64(t.y, v.x, cim, 0, 0, 0);
+    }
+}
+
+// TRSM of one 16-row tile (cop: per-lane registers, C[li][lk + 4s]) against the factored
+// diagonal block of the sub-panel at column c0 (inverse Di): L = C D^{-H}, written to R; y rows
+// updated with the sub-panel's y block yb.  Returns X[li][lk + 4q] in xv (the A-operand layout
+// of k-step q) and the updated y components in yd.
 // The y update Y_tile -= X Y_blk is two real MFMA GEMMs over the 16 columns of X with the
 // right-hand sides embedded as 2*NR real columns (re | im): A = Re X, Im X (= xv as it
 // comes out of the TRSM), B1 = [Re Y | Im Y], B2 = [-Im Y | Re Y]; lane (li, lk) ends with
 // component (li < NR: re, else im) of right-hand side li mod NR for rows lk + 4q, and
 // yd[q] holds the same component of those rows before the update (load_ycomp).  NR <= 8.
 template <bool G3 = false>
-__device__ __forceinline__ void trsm_tile16(cd* R, cd* y, const cd* Di, const cd* X, const cd* yb,
+__device__ __forceinline__ void trsm_tile16(cd* R, cd* y, const cd* Di, const cd* cop, const cd* yb,
                                             int L, int NR, int row0, int c0, int w, int li,
-                                            int lk, cd* xv, const double* yd, cd* ylds = nullptr) {
+                                            int lk, cd* xv, double* yd, cd* ylds = nullptr) {
     d4v xre = {0.0, 0.0, 0.0, 0.0}, xim = {0.0, 0.0, 0.0, 0.0}, x2 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int s2 = 0; s2 < NB / 4; ++s2) {
         const cd d = Di[li * NB + 4 * s2 + lk];    // A[j][k] = conj(Di[j][4s+k])
-        const cd c = X[li * NB + 4 * s2 + lk];     // B[k][i] = C[i][4s+k]
+        const cd c = cop[s2];                      // B[k][i] = C[i][4s+k]
         // X^T = conj(Di) C^T:  re += dr cr + di ci ;  im += dr ci - di cr
         if constexpr (G3) {       // P1 = dr cr, P2 = di ci, P3 = (dr + di)(cr - ci): im = P1 - P2 - P3
             xre = __builtin_amdgcn_mfma_f64_16x16x4f64(d.x, c.x, xre, 0, 0, 0);
@@ -946,6 +979,7 @@ __device__ __forceinline__ void trsm_tile16(cd* R, cd* y, const cd* Di, const cd
             if (row0 + rr < L) ((double*)(y + (size_t)(row0 + rr) * NR + r))[isre ? 0 : 1] = yn;
             // the updated rows also to LDS (zero past L) when the caller solves them next
             if (ylds) ((double*)(ylds + rr * NR + r))[isre ? 0 : 1] = row0 + rr < L ? yn : 0.0;
+            yd[q] = yn;
         }
     }
 }
@@ -965,40 +999,117 @@ __device__ __forceinline__ void load_ycomp(const cd* y, int L, int NR, int row0,
 }
 
 // panel_factor_kernel: one workgroup (4 waves) per trial, panel [jb, jb+32) as sub-panels
-// A = [jb, jb+16) and B = [jb+16, jb+32):
-//   wave 0: factor A's diagonal tile (factor_diag_lds), D_A^-1 y_A, TRSM of row tile 1
-//           (X_A1, kept in LDS);                                                 barrier
-//   wave 0: C_B1 -= X_A1 X_A1^H, factor it (B's diagonal tile), D_B^-1 y_B;
-//   waves 1-3, row tiles tau >= 2: TRSM against D_A, then the in-panel rank-16 update
-//           C_B,tau -= X_A,tau X_A1^H written back to R;                          barrier
-//   all waves, tau >= 2: TRSM of C_B,tau against D_B.
-// LDS of the factor body (cd entries): Xs (4 waves' 16 x 16 scratch), DiA, DiB, XA1, ybA, ybB
-constexpr int kFacXs = 0, kFacDiA = 4 * NB * NB, kFacDiB = kFacDiA + NB * NB, kFacXA1 = kFacDiB + NB * NB,
-              kFacYbA = kFacXA1 + NB * NB, kFacYbB = kFacYbA + NB * 8, kFacLds = kFacYbB + NB * 8;
-template <bool G3 = false>
-__device__ __forceinline__ void panel_preupdate(const MstepArgs& a, int L, int jb, int ntile, int b,
-                                                cd* Lp);
-template <bool G3 = false, bool CLK = false>
+// A = [jb, jb+16) and B = [jb+16, jb+32).  Every 16-row tile of the panel is read from R once,
+// kept in registers through all its steps and written once; a wave owns its tiles for the
+// whole launch (wave 0: the two diagonal tiles; wave w >= 1: row tiles 1 + w + 3k).
+// PRE (wide schedule, odd panels): the rank-32 update of the panel by the previous panel's
+// columns [jb-32, jb) (the part panel_update2_kernel left) is the first step of every tile,
+// its result staying in the accumulators (preupdate_half).
+//   all:    (PRE) stage Lp;                                                       barrier 0
+//   wave 0: (PRE) pre-update of tile 0's A half; factor A's diagonal tile (factor_diag_lds),
+//           D_A^-1 y_A; (PRE) pre-update of tile 1, which arrived by LDS-DMA meanwhile; TRSM of
+//           row tile 1 (X_A1, kept in LDS);
+//   waves 1-3: (PRE) loads and pre-update of their first tile;                    barrier 1
+//   wave 0: C_B1 -= X_A1 X_A1^H, factor it (B's diagonal tile), D_B^-1 y_B, then pubB = 1;
+//   waves 1-3, per tile: (PRE) pre-update, TRSM against D_A, the in-panel rank-16 update
+//           C_B -= X_A X_A1^H of the B half, then ONE look at pubB (never a wait):
+//             set:   TRSM of the B half against D_B from the registers (direct route);
+//             unset: the B half is stored to R and the tile queued in defl;       barrier 2
+//   all waves: the queued tiles' B halves, reloaded, TRSM against D_B (deferred route).
+// Both routes run the same instructions on the same values (the deferred one through an exact
+// store and reload), so the result does not depend on the route a tile took.
+// The tiles are held transposed (load_tileT's layout): the updates run with their MFMA operands
+// exchanged (csubT_step), so their output is the next TRSM's operand as it stands.
+//
+// LDS (cd entries from sm; who writes, who reads, what separates them):
+//   X0    wave 0's 16 x 16 scratch (diagonal tile being factored; even panels: also tile 1's
+//         transposition).  Wave 0 only, ordered by wave_sync.
+//   DiA   D_A^-1.  Written by wave 0 (factor A) before barrier 1, read by every wave after it.
+//   XA1   PRE: row tile 1's A half by LDS-DMA (wave 0, issued before factor A, read back by
+//         wave 0 after it: s_waitcnt vmcnt(0) + wave_sync).  Then X_A of row tile 1, written by
+//         wave 0 before barrier 1, read by every wave after it.
+//   ybA   y block A after D_A^-1.  As DiA.
+//   DiB   B's diagonal tile: by LDS-DMA (wave 0, before barrier 1; PRE: read back, pre-updated
+//         and rewritten by wave 0), read by wave 0 alone after barrier 1.  Then D_B^-1, written
+//         by wave 0 (factor B).  Other waves read it only after an acquire load of pubB
+//         returned 1 (set by wave 0 with a workgroup release after its LDS stores completed)
+//         or after barrier 2.
+//   ybB   tile 1's updated y rows (wave 0, before barrier 1), solved in place by wave 0 after
+//         barrier 1.  Other waves: as DiB.
+//   tail  PRE: Lp, panel j-1's rows jb .. jb+31 (PW x (PW+1)), written by all threads before
+//         barrier 0, read-only afterwards (waves 1-3 until barrier 2, wave 0 before factor A).
+//         Even panels: waves 1-3's 16 x 16 transposition scratch, one per wave, private.
+//   dinv  wave 0 only.   ctl[0] status flag: wave 0 writes, thread 0 reads after barrier 2.
+//   ctl[1] pubB (above).  ctl[2] number of queued tiles and defl[]: LDS atomics of waves 1-3
+//         before barrier 2, read by all after it.
+// No region is aliased with another inside a launch.
+constexpr int kFacX0 = 0, kFacDiA = NB * NB, kFacDiB = 2 * NB * NB, kFacXA1 = 3 * NB * NB,
+              kFacYbA = 4 * NB * NB, kFacYbB = kFacYbA + NB * 8, kFacTail = kFacYbB + NB * 8,
+              kFacLdsEven = kFacTail + 3 * NB * NB, kFacLdsPre = kFacTail + PW * (PW + 1);
+constexpr int kFacMaxTile = (kLargeL + NB - 1) / NB;
+
+// Rank-PW update of one 16 x 16 half tile c (transposed layout, in and out) by panel j-1's
+// columns: C -= A conj(Lp)^T, A = the tile's rows of [jb-32, jb) (av[4 kk + s] = column
+// 16 kk + 4 s + lk of row li), Lph = the half's 16 rows of Lp.
+template <bool G3>
+__device__ __forceinline__ void preupdate_half(const cd* Lph, const cd* av, cd* c, int li, int lk) {
+    d4v cre, cim, c2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        cre[q] = c[q].x;
+        cim[q] = c[q].y;
+    }
+    csub_init<G3>(cre, cim, c2);
+#pragma unroll
+    for (int kk = 0; kk < PW / NB; ++kk)
+#pragma unroll
+        for (int s2 = 0; s2 < 4; ++s2)
+            csubT_step<G3>(cre, cim, c2, av[4 * kk + s2], Lph[li * (PW + 1) + NB * kk + 4 * s2 + lk]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) c[q] = csub_out<G3>(cre, cim, c2, q);
+}
+
+// a tile's rows of panel j-1's columns [k0c, k0c + 32) (rows past L: row L-1, harmless reads)
+__device__ __forceinline__ void load_arow(const cd* R, int L, int row0, int k0c, int li, int lk,
+                                          bool on, cd* av) {
+    int r = row0 + li;
+    r = r < L ? r : L - 1;
+    const cd* arow = R + (size_t)r * L + k0c + lk;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) av[s] = on ? arow[4 * s] : czero();
+}
+
+// entries past the matrix or the sub-panel are zero for the TRSM (as a reload would give)
+__device__ __forceinline__ void mask_tileT(cd* c, int L, int row0, int w, int li, int lk) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (!(row0 + li < L && lk + 4 * q < w)) c[q] = czero();
+}
+
+template <bool G3 = false, bool PRE = false, bool CLK = false>
 __device__ __forceinline__ void panel_factor_body(const MstepArgs& a, int L, int NR, int jb, int ntile,
-                                                  int b, int skip, cd* sm, double* dinv, int& flag,
-                                                  unsigned long long t_start = 0) {
+                                                  int b, int skip, cd* sm, double* dinv, int* ctl,
+                                                  int* defl, unsigned long long t_start = 0) {
     // skip: DIAGNOSTIC phase mask (timing only, results invalid): 2 diag factors, 8 trsm tiles
+    // (bit 1, the updates, no longer reaches the odd panels' pre-update: it is part of the tiles)
+    cd* X0 = sm + kFacX0;
     cd* DiA = sm + kFacDiA;
     cd* DiB = sm + kFacDiB;
     cd* XA1 = sm + kFacXA1;
-    cd* Xs = sm + kFacXs;
     cd* ybA = sm + kFacYbA;     // the sub-panels' y blocks after D^-1
     cd* ybB = sm + kFacYbB;
+    cd* Lp = sm + kFacTail;     // PRE
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lk = lane >> 4;
     const int w2 = (L - jb) < PW ? (L - jb) : PW;
     const int wA = w2 < NB ? w2 : NB, wB = w2 - NB;          // wB <= 0: no sub-panel B
-    const int jbB = jb + NB;
+    const int jbB = jb + NB, k0c = jb - PW;
     const double tol = a.tol[b];
     cd* R = a.R + (size_t)b * L * L;
     cd* y = a.rhs + (size_t)b * L * NR;
-    cd* X = Xs + wave * NB * NB;
+    cd* X = wave ? sm + kFacTail + (wave - 1) * NB * NB : X0;    // even panels' scratch
+    int* flag = ctl;
     const bool trsm = !(skip & 8);
     // DIAGNOSTIC (skip & 64, trial 0 only): per-phase s_memtime sums of waves 0 and 1 in
     // g_chol_clk[16 + 8 wave + phase] (timing only; results unchanged)
@@ -1011,64 +1122,137 @@ __device__ __forceinline__ void panel_factor_body(const MstepArgs& a, int L, int
             tclk = t2;
         }
     };
-    if (tid == 0) flag = 0;
-    __syncthreads();
+    if (tid < 3) ctl[tid] = 0;
+    if constexpr (PRE) {
+        for (int e = tid; e < PW * PW; e += 256) {
+            const int c = e >> 5, k = e & (PW - 1);
+            Lp[c * (PW + 1) + k] = c < w2 ? R[(size_t)(jb + c) * L + k0c + k] : czero();
+        }
+    }
+    __syncthreads();                                             // barrier 0
     stamp(0);
     cd xv[4];
-    // waves 1-3: their first row tile (A part) and y rows are in flight while wave 0 factors
-    cd cur[4];
+    // waves 1-3: their first row tile is loaded (PRE: and pre-updated) while wave 0 factors;
+    // ca / cb: the tile's A and B halves, transposed (even panels: the A half as load_tile16
+    // gives it, transposed through X inside the loop)
+    cd ca[4], cb[4], av[8];
     double ycur[4];
+    int tau = 1 + wave;
     if (wave != 0) {
-        const int tau = 1 + wave;
-        load_tile16(R, L, jb + tau * NB, jb, wA, lane, trsm && tau < ntile, cur);
-        load_ycomp(y, L, NR, jb + tau * NB, li, lk, trsm && tau < ntile, ycur);
-    }
-    // wave 0's serial chain reads every global operand up front: B's diagonal tile (written
-    // by no one in this launch) arrives by LDS-DMA in DiB (unused until factor B; no
-    // registers held across factor A), y block A in ybA, before factor A starts
-    if (wave == 0) {
-        __builtin_amdgcn_s_setprio(3);                       // the serial chain issues first
-        cd t1[4];
-        double y1[4];
-        load_tile16(R, L, jbB, jb, wA, lane, ntile > 1, t1);        // row tile 1, A part
-        load_ycomp(y, L, NR, jbB, li, lk, ntile > 1, y1);
-        if (wB > 0) {
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {          // DiB[e] = R[jbB + e/16][jbB + e%16]
-                const int e = lane + 64 * h, rr = e >> 4, c = e & 15;
-                const cd* src = R + (size_t)(jbB + (rr < wB ? rr : 0)) * L + jbB + (c < wB ? c : 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(DiB + 64 * h),
-                                                 16, 0, 0);
-            }
+        const bool on = trsm && tau < ntile;
+        const int row0 = jb + tau * NB;
+        if constexpr (PRE) {
+            load_arow(R, L, row0, k0c, li, lk, on, av);
+            load_tileT(R, L, row0, jb, wA, li, lk, on, ca);
+            load_tileT(R, L, row0, jbB, wB, li, lk, on, cb);
+            if (on) preupdate_half<G3>(Lp, av, ca, li, lk);
+            if (on && wB > 0) preupdate_half<G3>(Lp + NB * (PW + 1), av, cb, li, lk);
+        } else {
+            load_tile16(R, L, row0, jb, wA, lane, on, ca);
+            load_ycomp(y, L, NR, row0, li, lk, on, ycur);
         }
-        for (int e = lane; e < NB * NR; e += 64) ybA[e] = (e < wA * NR) ? y[jb * NR + e] : czero();
-        for (int e = lane; e < NB * NB; e += 64) {
-            const int rr = e >> 4, c = e & 15;
-            X[e] = (rr < wA && c <= rr) ? R[(size_t)(jb + rr) * L + jb + c] : czero();
+        stamp(1);
+    } else {
+        // wave 0 owns row tile 1: its halves in ca / cb (cb = B's diagonal tile, PRE), y rows in ycur
+        __builtin_amdgcn_s_setprio(3);                       // the serial chain issues first
+        if constexpr (PRE) {
+            // the two diagonal tiles are pre-updated here (their rows of panel j-1 are Lp's):
+            // tile 0's A half into X0 (lower part) before factor A; tile 1's halves arrive by
+            // LDS-DMA in XA1 and DiB (both unused until after factor A, no registers held
+            // across it) and are pre-updated after it
+            cd d0[4];
+            load_tileT(R, L, jb, jb, wA, li, lk, true, d0);
+            load_ycomp(y, L, NR, jbB, li, lk, ntile > 1, ycur);
+            if (wB > 0) {
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {          // XA1[e] = R[jbB + e/16][jb + e%16], DiB: column jbB
+                    const int e = lane + 64 * h, rr = e >> 4, c = e & 15;
+                    const cd* src = R + (size_t)(jbB + (rr < wB ? rr : 0)) * L;
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + jb + c),
+                                                     (__attribute__((address_space(3))) void*)(XA1 + 64 * h),
+                                                     16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + jbB + (c < wB ? c : 0)),
+                                                     (__attribute__((address_space(3))) void*)(DiB + 64 * h),
+                                                     16, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 8; ++s) av[s] = Lp[li * (PW + 1) + 4 * s + lk];
+            for (int e = lane; e < NB * NR; e += 64) ybA[e] = (e < wA * NR) ? y[jb * NR + e] : czero();
+            preupdate_half<G3>(Lp, av, d0, li, lk);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = lk + 4 * q;
+                X0[li * NB + c] = (li < wA && c <= li) ? d0[q] : czero();
+            }
+        } else {
+            // wave 0's serial chain reads every global operand up front: B's diagonal tile
+            // (written by no one in this launch) arrives by LDS-DMA in DiB (unused until
+            // factor B; no registers held across factor A), y block A in ybA
+            load_tile16(R, L, jbB, jb, wA, lane, ntile > 1, ca);        // row tile 1, A part
+            load_ycomp(y, L, NR, jbB, li, lk, ntile > 1, ycur);
+            if (wB > 0) {
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {          // DiB[e] = R[jbB + e/16][jbB + e%16]
+                    const int e = lane + 64 * h, rr = e >> 4, c = e & 15;
+                    const cd* src = R + (size_t)(jbB + (rr < wB ? rr : 0)) * L + jbB + (c < wB ? c : 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                     (__attribute__((address_space(3))) void*)(DiB + 64 * h),
+                                                     16, 0, 0);
+                }
+            }
+            for (int e = lane; e < NB * NR; e += 64) ybA[e] = (e < wA * NR) ? y[jb * NR + e] : czero();
+            for (int e = lane; e < NB * NB; e += 64) {
+                const int rr = e >> 4, c = e & 15;
+                X0[e] = (rr < wA && c <= rr) ? R[(size_t)(jb + rr) * L + jb + c] : czero();
+            }
         }
         wave_sync();
         stamp(1);
         if (!(skip & 2)) {
-            factor_diag_lds(X, wA, lane, tol, a.solve_mode, DiA, dinv, &flag,
+            factor_diag_lds(X0, wA, lane, tol, a.solve_mode, DiA, dinv, flag,
                             R + (size_t)jb * L + jb, L);
             forward_y_lds(DiA, ybA, y + jb * NR, wA, NR, lane);
         }
         wave_sync();
         stamp(2);
-        if (ntile > 1 && trsm) {
+        if constexpr (PRE) {
+            if (wB > 0) {                                    // <=> ntile > 1
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile 1 is in XA1 / DiB
+                wave_sync();
 #pragma unroll
-            for (int h = 0; h < 4; ++h) X[lane + 64 * h] = t1[h];
-            wave_sync();
+                for (int s = 0; s < 8; ++s) av[s] = Lp[(NB + li) * (PW + 1) + 4 * s + lk];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    ca[q] = XA1[li * NB + lk + 4 * q];
+                    cb[q] = DiB[li * NB + lk + 4 * q];
+                }
+                wave_sync();                                 // XA1 is overwritten next
+                preupdate_half<G3>(Lp, av, ca, li, lk);
+                mask_tileT(ca, L, jbB, wA, li, lk);
+                preupdate_half<G3>(Lp + NB * (PW + 1), av, cb, li, lk);
+                // B's diagonal tile waits in DiB (as the even panels' does), not in registers
+#pragma unroll
+                for (int q = 0; q < 4; ++q) DiB[li * NB + lk + 4 * q] = cb[q];
+            }
+        }
+        if (ntile > 1 && trsm) {
+            if constexpr (!PRE) {
+#pragma unroll
+                for (int h = 0; h < 4; ++h) X0[lane + 64 * h] = ca[h];
+                wave_sync();
+#pragma unroll
+                for (int s2 = 0; s2 < 4; ++s2) ca[s2] = X0[li * NB + 4 * s2 + lk];
+            }
             // row tile 1 = sub-panel B's rows: its updated y rows are staged raw in ybB
-            trsm_tile16<G3>(R, y, DiA, X, ybA, L, NR, jbB, jb, wA, li, lk, xv, y1, ybB);
+            trsm_tile16<G3>(R, y, DiA, ca, ybA, L, NR, jbB, jb, wA, li, lk, xv, ycur, ybB);
 #pragma unroll
             for (int q = 0; q < 4; ++q) XA1[li * NB + lk + 4 * q] = xv[q];
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // B's diagonal tile is in DiB
+        if constexpr (!PRE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // B's diagonal tile is in DiB
         stamp(3);
     }
-    __syncthreads();
+    __syncthreads();                                             // barrier 1
     stamp(4);
     if (wave == 0) {
         if (wB > 0) {
@@ -1076,181 +1260,139 @@ __device__ __forceinline__ void panel_factor_body(const MstepArgs& a, int L, int
             d4v cre = {0.0, 0.0, 0.0, 0.0}, cim = {0.0, 0.0, 0.0, 0.0}, c2;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int rr = lk + 4 * q;
-                if (rr < wB && li < wB) {
-                    const cd x = DiB[rr * NB + li];
+                const int c = lk + 4 * q;
+                if (li < wB && c < wB) {
+                    const cd x = DiB[li * NB + c];
                     cre[q] = x.x;
                     cim[q] = x.y;
                 }
             }
             wave_sync();                                         // DiB is overwritten next
             csub_init<G3>(cre, cim, c2);
+            // both operands from XA1 (X_A1[li][4s + lk]): nothing is held across barrier 1
 #pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) csub_step<G3>(cre, cim, c2, xv[s2], XA1[li * NB + 4 * s2 + lk]);
+            for (int s2 = 0; s2 < 4; ++s2) {
+                const cd x1 = XA1[li * NB + 4 * s2 + lk];
+                csubT_step<G3>(cre, cim, c2, x1, x1);
+            }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) X[(lk + 4 * q) * NB + li] = csub_out<G3>(cre, cim, c2, q);
+            for (int q = 0; q < 4; ++q) X0[li * NB + lk + 4 * q] = csub_out<G3>(cre, cim, c2, q);
             wave_sync();
             if (!(skip & 2)) {
-                factor_diag_lds(X, wB, lane, tol, a.solve_mode, DiB, dinv, &flag,
+                factor_diag_lds(X0, wB, lane, tol, a.solve_mode, DiB, dinv, flag,
                                 R + (size_t)jbB * L + jbB, L);
                 forward_y_lds(DiB, ybB, y + jbB * NR, wB, NR, lane);
             }
+            // D_B^-1 and y block B are published once this wave's LDS stores have completed
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) __hip_atomic_store(&ctl[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-    } else if (trsm) {
-        // row tiles tau >= 2: TRSM against D_A, in-panel update of their B part
-        int tau = 1 + wave;
-        for (; tau < ntile; tau += 3) {
+    } else {
+        // this wave's row tiles: TRSM against D_A, in-panel update of the B half, then TRSM
+        // against D_B if it is there already
+        while (trsm && tau < ntile) {
             const int row0 = jb + tau * NB;
+            const bool more = tau + 3 < ntile;
+            double yv[4] = {ycur[0], ycur[1], ycur[2], ycur[3]};
+            if constexpr (PRE) {
+                // the y rows (a few L2 lines) arrive under the TRSM's MFMAs: held from the
+                // tile's other loads they cost the registers the pre-update needs
+                load_ycomp(y, L, NR, row0, li, lk, true, yv);
+                mask_tileT(ca, L, row0, wA, li, lk);
+            } else {
 #pragma unroll
-            for (int h = 0; h < 4; ++h) X[lane + 64 * h] = cur[h];
-            d4v cre = {0.0, 0.0, 0.0, 0.0}, cim = {0.0, 0.0, 0.0, 0.0}, c2;
+                for (int h = 0; h < 4; ++h) X[lane + 64 * h] = ca[h];
+                load_tileT(R, L, row0, jbB, wB, li, lk, true, cb);
+                wave_sync();
+            }
+            cd cop[4];
+#pragma unroll
+            for (int s2 = 0; s2 < 4; ++s2) cop[s2] = PRE ? ca[s2] : X[li * NB + 4 * s2 + lk];
+            trsm_tile16<G3>(R, y, DiA, cop, ybA, L, NR, row0, jb, wA, li, lk, xv, yv);
+            if constexpr (!PRE) {
+                // the next tile's A half and y rows are in flight from here
+                load_tile16(R, L, row0 + 3 * NB, jb, wA, lane, more, ca);
+                load_ycomp(y, L, NR, row0 + 3 * NB, li, lk, more, ycur);
+            }
             if (wB > 0) {
+                d4v cre, cim, c2;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int rr = row0 + lk + 4 * q;
-                    if (rr < L && li < wB) {
-                        const cd x = R[(size_t)rr * L + jbB + li];
-                        cre[q] = x.x;
-                        cim[q] = x.y;
-                    }
+                    cre[q] = cb[q].x;
+                    cim[q] = cb[q].y;
                 }
-            }
-            const double yv[4] = {ycur[0], ycur[1], ycur[2], ycur[3]};
-            load_tile16(R, L, row0 + 3 * NB, jb, wA, lane, tau + 3 < ntile, cur);   // next
-            load_ycomp(y, L, NR, row0 + 3 * NB, li, lk, tau + 3 < ntile, ycur);
-            wave_sync();
-            trsm_tile16<G3>(R, y, DiA, X, ybA, L, NR, row0, jb, wA, li, lk, xv, yv);
-            if (wB > 0) {
                 csub_init<G3>(cre, cim, c2);
 #pragma unroll
-                for (int s2 = 0; s2 < 4; ++s2) csub_step<G3>(cre, cim, c2, xv[s2], XA1[li * NB + 4 * s2 + lk]);
+                for (int s2 = 0; s2 < 4; ++s2) csubT_step<G3>(cre, cim, c2, xv[s2], XA1[li * NB + 4 * s2 + lk]);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int rr = row0 + lk + 4 * q;
-                    if (rr < L && li < wB) R[(size_t)rr * L + jbB + li] = csub_out<G3>(cre, cim, c2, q);
+                for (int q = 0; q < 4; ++q) cb[q] = csub_out<G3>(cre, cim, c2, q);
+                mask_tileT(cb, L, row0, wB, li, lk);
+                // one look, never a wait: D_B^-1 there -> finish the tile from the registers
+                const int pub = __builtin_amdgcn_readfirstlane(
+                    __hip_atomic_load(&ctl[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+                if (pub) {
+                    trsm_tile16<G3>(R, y, DiB, cb, ybB, L, NR, row0, jbB, wB, li, lk, xv, yv);
+                } else {
+                    if (row0 + li < L) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (lk + 4 * q < wB) R[(size_t)(row0 + li) * L + jbB + lk + 4 * q] = cb[q];
+                    }
+                    if (lane == 0) defl[atomicAdd(&ctl[2], 1)] = tau;
                 }
             }
-            wave_sync();
+            if constexpr (!PRE) wave_sync();                     // X is rewritten next
+            tau += 3;
+            if constexpr (PRE) {
+                // the next tile: every load issued at once, where nothing else is held (the
+                // other waves of the SIMD cover the latency; a prefetch across the TRSMs spills)
+                if (tau < ntile) {
+                    load_arow(R, L, row0 + 3 * NB, k0c, li, lk, true, av);
+                    load_tileT(R, L, row0 + 3 * NB, jb, wA, li, lk, true, ca);
+                    load_tileT(R, L, row0 + 3 * NB, jbB, wB, li, lk, true, cb);
+                    preupdate_half<G3>(Lp, av, ca, li, lk);
+                    if (wB > 0) preupdate_half<G3>(Lp + NB * (PW + 1), av, cb, li, lk);
+                }
+            }
         }
     }
     stamp(5);
-    __syncthreads();
+    __syncthreads();                                             // barrier 2
     stamp(6);
     if (wB > 0 && trsm) {
-        // row tiles tau >= 2: TRSM of the updated B part against D_B
-        int tau = 2 + wave;
-        load_tile16(R, L, jb + tau * NB, jbB, wB, lane, tau < ntile, cur);
-        load_ycomp(y, L, NR, jb + tau * NB, li, lk, tau < ntile, ycur);
-        for (; tau < ntile; tau += 4) {
-            const int row0 = jb + tau * NB;
-#pragma unroll
-            for (int h = 0; h < 4; ++h) X[lane + 64 * h] = cur[h];
-            const double yv[4] = {ycur[0], ycur[1], ycur[2], ycur[3]};
-            load_tile16(R, L, row0 + 4 * NB, jbB, wB, lane, tau + 4 < ntile, cur);
-            load_ycomp(y, L, NR, row0 + 4 * NB, li, lk, tau + 4 < ntile, ycur);
-            wave_sync();
-            trsm_tile16<G3>(R, y, DiB, X, ybB, L, NR, row0, jbB, wB, li, lk, xv, yv);
-            wave_sync();
+        // the queued tiles: TRSM of the stored B half against D_B, dealt over all four waves
+        const int nd = ctl[2];
+        int i = wave;
+        int t = i < nd ? defl[i] : 0;
+        load_tileT(R, L, jb + t * NB, jbB, wB, li, lk, i < nd, cb);
+        load_ycomp(y, L, NR, jb + t * NB, li, lk, i < nd, ycur);
+        for (; i < nd; i += 4) {
+            const int row0 = jb + t * NB;
+            cd cop[4] = {cb[0], cb[1], cb[2], cb[3]};
+            double yv[4] = {ycur[0], ycur[1], ycur[2], ycur[3]};
+            t = i + 4 < nd ? defl[i + 4] : 0;
+            load_tileT(R, L, jb + t * NB, jbB, wB, li, lk, i + 4 < nd, cb);
+            load_ycomp(y, L, NR, jb + t * NB, li, lk, i + 4 < nd, ycur);
+            trsm_tile16<G3>(R, y, DiB, cop, ybB, L, NR, row0, jbB, wB, li, lk, xv, yv);
         }
     }
     stamp(7);
-    const int st = ((flag & 1) ? a.clamp_status : 0) | ((flag & 2) ? SBCE_STATUS_RANK : 0) |
+    const int st = ((*flag & 1) ? a.clamp_status : 0) | ((*flag & 2) ? SBCE_STATUS_RANK : 0) |
                    ((skip & 31) ? SBCE_STATUS_DEBUG : 0);
     if (tid == 0 && st && a.status) atomicOr(&a.status[b], st);
 }
 
-// PRE (wide schedule, odd panels): the rank-32 update of the panel by the previous panel's
-// columns [jb-32, jb) (the part panel_update2_kernel left) inside the factor launch, first
-// (panel_preupdate), then the factor.
 template <bool G3 = false, bool PRE = false, bool CLK = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 void panel_factor_kernel(MstepArgs a, int L, int NR, int jb, int ntile, int skip) {
-    __shared__ __attribute__((aligned(16))) cd sm[kFacLds];
+    __shared__ __attribute__((aligned(16))) cd sm[PRE ? kFacLdsPre : kFacLdsEven];
     __shared__ double dinv[NB];
-    __shared__ int flag;
+    __shared__ int ctl[4];
+    __shared__ int defl[kFacMaxTile];
     const int b = blockIdx.x;
     if (a.done && a.done[b]) return;
     const unsigned long long t0 = CLK ? __builtin_amdgcn_s_memtime() : 0;   // diagnostic
-    if (PRE && !(skip & 1)) panel_preupdate<G3>(a, L, jb, ntile, b, sm);
-    panel_factor_body<G3, CLK>(a, L, NR, jb, ntile, b, skip, sm, dinv, flag, t0);
-}
-
-// ---------------------------------------------------------------- look-ahead panel step
-// Rank-PW update of panel j (columns [jb, jb+32), every row tile) by panel j-1's columns
-// [jb-32, jb), written back to R: the part of panel j's left-looking update that the
-// look-ahead step could not make in the previous launch (panel j-1 was being factored there).
-// Lp: PW * (PW + 1) LDS entries (panel j-1's rows jb .. jb+31, the shared B operand).
-template <bool G3>
-__device__ __forceinline__ void panel_preupdate(const MstepArgs& a, int L, int jb, int ntile, int b,
-                                                cd* Lp) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, lk = lane >> 4;
-    const int w2 = (L - jb) < PW ? (L - jb) : PW;
-    const int k0c = jb - PW;
-    cd* R = a.R + (size_t)b * L * L;
-    for (int e = tid; e < PW * PW; e += 256) {
-        const int c = e >> 5, k = e & (PW - 1);
-        Lp[c * (PW + 1) + k] = c < w2 ? R[(size_t)(jb + c) * L + k0c + k] : czero();
-    }
-    __syncthreads();
-    for (int tau = wave; tau < ntile; tau += 4) {             // wave-uniform
-        const int row0 = jb + tau * NB;
-        int r = row0 + li;
-        r = r < L ? r : L - 1;                                   // rows past L: harmless reads
-        const cd* arow = R + (size_t)r * L + k0c + lk;
-        cd av[4];
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) av[s2] = arow[4 * s2];
-        const int nv = tau == 0 ? 1 : 2;                         // tile 0's right half: upper triangle
-        d4v cre[2], cim[2], c2[2];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            cre[v] = d4v{0.0, 0.0, 0.0, 0.0};
-            cim[v] = d4v{0.0, 0.0, 0.0, 0.0};
-            c2[v] = d4v{0.0, 0.0, 0.0, 0.0};
-            if (v < nv) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int rr = row0 + lk + 4 * q, c = 16 * v + li;
-                    if (rr < L && c < w2) {
-                        const cd x = R[(size_t)rr * L + jb + c];
-                        cre[v][q] = x.x;
-                        cim[v][q] = x.y;
-                    }
-                }
-            }
-            csub_init<G3>(cre[v], cim[v], c2[v]);
-        }
-#pragma unroll 1
-        for (int k0 = 0; k0 < PW; k0 += 16) {
-            cd an[4];
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) an[s2] = k0 == 0 ? arow[16 + 4 * s2] : czero();
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                const cd v = av[s2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    if (h >= nv) break;                          // wave-uniform
-                    // C -= A conj(B)^T (three real MFMAs per complex product with G3)
-                    csub_step<G3>(cre[h], cim[h], c2[h], v, Lp[(16 * h + li) * (PW + 1) + k0 + 4 * s2 + lk]);
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) av[s2] = an[s2];
-        }
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            if (v >= nv) break;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int rr = row0 + lk + 4 * q, c = 16 * v + li;
-                if (rr < L && c < w2) R[(size_t)rr * L + jb + c] = csub_out<G3>(cre[v], cim[v], c2[v], q);
-            }
-        }
-    }
-    __syncthreads();
+    panel_factor_body<G3, PRE, CLK>(a, L, NR, jb, ntile, b, skip, sm, dinv, ctl, defl, t0);
 }
 
 // ---------------------------------------------------------------- back substitution

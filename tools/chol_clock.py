@@ -21,8 +21,10 @@ eng.estep()
 eng.mstep()
 torch.cuda.synchronize()
 out = (ctypes.c_ulonglong * 32)()
-names = ["start/PRE", "wave0 loads", "factor A", "tile-1 TRSM", "sync 1", "B chain | TRSM A",
-         "sync 2", "TRSM B"]
+# wave 0 | wave 1 where they differ (odd panels: "loads" include the pre-update of tile 0 /
+# of the wave's first tile; "tile 1" its LDS-DMA wait, pre-update and TRSM)
+names = ["start, Lp staging", "loads (+ pre-upd)", "factor A", "tile 1", "sync 1",
+         "B chain | tile loop", "sync 2", "deferred TRSM B"]
 reps = int(os.environ.get("REPS", "5"))
 LIB.sbce_debug_chol_skip(64)
 LIB.sbce_debug_chol_clock(None, 1)
@@ -34,5 +36,5 @@ LIB.sbce_debug_chol_skip(0)
 print(f"B={B}: cycles per M-step (9 factor launches), trial 0")
 for ph, nm in enumerate(names):
     w0, w1 = out[16 + ph] / reps, out[24 + ph] / reps
-    print(f"  {ph} {nm:18s} wave0 {w0:9.0f}  wave1 {w1:9.0f}")
+    print(f"  {ph} {nm:20s} wave0 {w0:9.0f}  wave1 {w1:9.0f}")
 print(f"  total              wave0 {sum(out[16:24]) / reps:9.0f}  wave1 {sum(out[24:32]) / reps:9.0f}")
