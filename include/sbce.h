@@ -340,6 +340,53 @@ int sbce_detect_workspace_bytes(const sbce_detect_dims* d, size_t* bytes);
  * 4 int32); SBCE_EUNSUPPORTED: n_tx > 4, n_rx > 8 or m^n_tx > 65536; SBCE_EWORKSPACE. */
 int sbce_detect(const sbce_detect_dims* d, const sbce_detect_ptrs* p, void* hip_stream);
 
+/* ---- EM with unknown noise variance (an additive extension of ABI 7: no existing struct or entry
+ * point changes).  The noise parameter is estimated per trial beside theta: after an M-step, from
+ * the new theta and the moments (m_t, S_t) of the same iteration's E-step,
+ *   Q       = sum_pilots ||y_p - H_c u_p||^2 + sum_data ( ||y_t - H_t m_t||^2 + tr(H_t C_t H_t^H) )
+ *   sigma^2 = Q / (n_rx (T_p + T_d)),      varn_est = sqrt(sigma^2)
+ * with C_t = S_t - m_t m_t^H and H_t[r][a] = sum_p psi_d[t][p] theta[(p n_tx + a) n_rx + r]
+ * (sbce_detect's channel, also in the PM modes).  The posterior of the next E-step divides by
+ * varn_est^2 = sigma^2: this is the exact M-step for the denominator, so with SBCE_ESTEP_SOFT the
+ * observed-data likelihood does not decrease.  Rules: sigma^2 < varn_min^2 gives varn_est =
+ * varn_min exactly and SBCE_STATUS_NOISE; a non-finite Q keeps the previous value, same bit.
+ * The sums are formed without atomics in an order fixed by (t_d, t_p, n_rx): a trial's result
+ * does not depend on the batch around it. */
+#define SBCE_STATUS_NOISE 64    /* the noise update hit its floor varn_min, or Q was not finite and
+                                   the previous parameter was kept */
+
+typedef struct sbce_noise_opts {
+    double* varn_est;     /* [B] out: the parameter after the last update a trial performed */
+    double* varn_hist;    /* may be NULL: [B][iters] out, the parameter after each iteration
+                             (sbce_noise_var: ignored) */
+    void* scratch;        /* device scratch, 8-byte aligned */
+    size_t scratch_bytes; /* at least sbce_noise_workspace_bytes */
+    double varn_min;      /* > 0: floor of the parameter */
+    int32_t flags;        /* 0 */
+} sbce_noise_opts;
+
+/* Device scratch of sbce_noise_var / sbce_em_noise for `d` (the block sums of Q). */
+int sbce_noise_workspace_bytes(const sbce_dims* d, size_t* bytes);
+
+/* One noise update of every trial from theta (p->theta, not written) and `moments` (sbce_estep's
+ * layout): two kernel launches on `hip_stream`, no memset, no allocation, no synchronisation;
+ * capturable in a HIP graph as a linear chain.  The previous value of the keep-previous rule is
+ * p->varn_t[b] (or d->varn); p->status, when set, is written (0 or SBCE_STATUS_NOISE).  p->cons
+ * and p->workspace are not used.  Errors as sbce_em_noise. */
+int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
+                   const sbce_noise_opts* o, void* hip_stream);
+
+/* sbce_em with the noise parameter estimated: varn_est[b] starts at p->varn_t[b] (or d->varn) and
+ * is the E-step's per-trial parameter; per iteration E-step, M-step, noise update, then the oracle
+ * early stop (p->h_true), so a trial's last M-step is followed by its update.  p->workspace as for
+ * sbce_em.  estep_mode: SOFT, HARD, PM, PM_SOFT, ZF, MMSE; SBCE_ESTEP_GAUSS gives
+ * SBCE_EUNSUPPORTED (its S_t is not a second moment).  Decided before any HIP call, beside
+ * sbce_em's own checks -- SBCE_EINVAL: p->x_sup or p->llf set, null or misaligned (8 bytes)
+ * varn_est, varn_hist or scratch, varn_min <= 0, flags != 0; SBCE_EWORKSPACE: scratch_bytes too
+ * small. */
+int sbce_em_noise(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode,
+                  int solve_mode, const sbce_noise_opts* o, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

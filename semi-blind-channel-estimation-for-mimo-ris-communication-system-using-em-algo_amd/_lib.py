@@ -31,13 +31,15 @@ SBCE_STATUS_DETECTOR = 4
 SBCE_STATUS_DEBUG = 8
 SBCE_STATUS_RANK = 16
 SBCE_STATUS_SINGULAR = 32
+SBCE_STATUS_NOISE = 64
 SBCE_DETECT_MAXLOG = 1
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_workspace_bytes_solve", "sbce_em",
             "sbce_estep", "sbce_mstep", "sbce_ser", "sbce_gauss_expand", "sbce_nmse",
             "sbce_approx_workspace_bytes", "sbce_approx_em",
-            "sbce_detect_workspace_bytes", "sbce_detect")
+            "sbce_detect_workspace_bytes", "sbce_detect",
+            "sbce_noise_workspace_bytes", "sbce_noise_var", "sbce_em_noise")
 
 
 class SbceUnavailable(RuntimeError):
@@ -93,6 +95,13 @@ class DetectPtrs(ctypes.Structure):
                 ("x_hat", ctypes.c_void_p), ("idx_hat", ctypes.c_void_p), ("post", ctypes.c_void_p),
                 ("llr", ctypes.c_void_p), ("err", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
                 ("workspace_bytes", ctypes.c_size_t)]
+
+
+class NoiseOpts(ctypes.Structure):
+    """sbce_noise_opts (include/sbce.h): the noise-variance update of sbce_noise_var / sbce_em_noise."""
+    _fields_ = [("varn_est", ctypes.c_void_p), ("varn_hist", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+                ("varn_min", ctypes.c_double), ("flags", ctypes.c_int32)]
 
 
 _lib = None
@@ -158,6 +167,15 @@ def load(path=None):
     lib.sbce_detect.restype = ctypes.c_int
     lib.sbce_detect.argtypes = [ctypes.POINTER(DetectDims), ctypes.POINTER(DetectPtrs),
                                 ctypes.c_void_p]
+    lib.sbce_noise_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_noise_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_noise_var.restype = ctypes.c_int
+    lib.sbce_noise_var.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_void_p,
+                                   ctypes.POINTER(NoiseOpts), ctypes.c_void_p]
+    lib.sbce_em_noise.restype = ctypes.c_int
+    lib.sbce_em_noise.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.POINTER(NoiseOpts),
+                                  ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

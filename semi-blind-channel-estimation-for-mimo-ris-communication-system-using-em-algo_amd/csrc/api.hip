@@ -199,6 +199,47 @@ int check_ptrs(const sbce_ptrs* p, const Problem& pb, bool need_ws, int solve = 
     return SBCE_OK;
 }
 
+// sbce_noise_opts against `pb` (sbce_noise_var, sbce_em_noise): decided before any HIP call
+size_t noise_scratch_bytes(const Problem& pb) {
+    return align_up((size_t)pb.B * noise_nblk(pb) * sizeof(double));
+}
+
+int check_noise(const sbce_ptrs* p, const sbce_noise_opts* o, const Problem& pb) {
+    if (!p || !o) return SBCE_EINVAL;
+    if (p->x_sup || p->llf) return SBCE_EINVAL;
+    if (!o->varn_est || ((uintptr_t)o->varn_est & 7) || ((uintptr_t)o->varn_hist & 7))
+        return SBCE_EINVAL;
+    if (!(o->varn_min > 0.0) || o->flags != 0) return SBCE_EINVAL;
+    if (!o->scratch || ((uintptr_t)o->scratch & 7)) return SBCE_EINVAL;
+    if (o->scratch_bytes < noise_scratch_bytes(pb)) return SBCE_EWORKSPACE;
+    return SBCE_OK;
+}
+
+// One noise update: the block sums of Q, then the per-trial rules.  fin (stand-alone call): the
+// previous value and the status word's base; null (inside the EM loop): the previous value is
+// varn_est itself, the flag is OR-ed into the status word and varn_hist[b][it] is written.
+int noise_update(const Problem& pb, const sbce_ptrs* p, const cd* mom, const int32_t* done,
+                 const sbce_noise_opts* o, const NoiseFinalArgs* fin, int iters, int it,
+                 hipStream_t s) {
+    NoiseArgs a{};
+    a.yd = (const cd*)p->y_d; a.yp = (const cd*)p->y_p; a.psid = (const cd*)p->psi_d;
+    a.up = (const cd*)p->u_p; a.theta = (const cd*)p->theta; a.mom = mom; a.done = done;
+    a.part = (double*)o->scratch;
+    int rc = hip_rc(launch_noise_partial(pb, a, s));
+    if (rc) return rc;
+    NoiseFinalArgs f{};
+    if (fin) {
+        f = *fin;
+    } else {
+        f.prev_t = o->varn_est;
+        f.status_base = -1;
+        f.hist = o->varn_hist;
+    }
+    f.part = a.part; f.done = done; f.varn_est = o->varn_est; f.status = p->status;
+    f.varn_min = o->varn_min; f.iters = iters; f.it = it;
+    return hip_rc(launch_noise_final(pb, f, s));
+}
+
 }  // namespace
 
 extern "C" {
@@ -233,11 +274,15 @@ int sbce_workspace_bytes_solve(const sbce_dims* d, int solve_mode, size_t* bytes
     return SBCE_OK;
 }
 
-int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
-            void* hip_stream) {
+// The EM loop of sbce_em and sbce_em_noise.  nz == nullptr: sbce_em.  nz: the noise parameter is
+// estimated (noise.hip): nz->varn_est is the E-step's per-trial parameter, updated after every
+// M-step, and the oracle early stop runs after the update in its own launch.
+static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+                  const sbce_noise_opts* nz, void* hip_stream) {
     clear_stale_error();
     Problem pb;
     if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
+    if (nz && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
     if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
     if (solve_mode != SBCE_SOLVE_CHOL && solve_mode != SBCE_SOLVE_CHOL_DROP &&
         solve_mode != SBCE_SOLVE_MINNORM)
@@ -253,6 +298,7 @@ int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, i
     if (p->x_sup && ((estep_mode != SBCE_ESTEP_SOFT && estep_mode != SBCE_ESTEP_HARD) ||
                      !aligned16(p->x_sup)))
         return SBCE_EINVAL;
+    if (nz && (rc = check_noise(p, nz, pb))) return rc;
     if (pb.B == 0 || iters == 0) return SBCE_OK;
     hipStream_t s = (hipStream_t)hip_stream;
     const Carve c = carve(pb, solve_mode);
@@ -274,6 +320,10 @@ int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, i
     ea.cons = (const cd*)p->cons; ea.mom = (cd*)(ws + c.mom); ea.done = early ? done : nullptr;
     ea.status = p->status;
     ea.varn_t = p->varn_t;
+    if (nz) {                                // the estimate starts at the caller's parameter
+        if ((rc = hip_rc(launch_noise_init(pb.B, nz->varn_est, p->varn_t, pb.varn, s)))) return rc;
+        ea.varn_t = nz->varn_est;
+    }
     ea.prep = c.has_prep ? (double*)(ws + c.prep) : nullptr;
     ea.list = c.has_prep ? (int32_t*)(ws + c.list) : nullptr;
     ea.tree = c.has_prep ? (double*)(ws + c.tree) : nullptr;
@@ -290,7 +340,8 @@ int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, i
     const bool prefactor = rbuild_herm_supported(pb);
     if (prefactor && (rc = hip_rc(launch_pilot_factor(pb, ma, s)))) return rc;
     // the LLF kernel reads theta before the stop decision of the same iteration: no fold with it
-    const bool fold_stop = small2 && early && !p->llf;
+    // nor with the noise update, which follows a trial's last M-step
+    const bool fold_stop = small2 && early && !p->llf && !nz;
     for (int it = 0; it < iters; ++it) {
         if (p->x_sup) {
             if ((rc = hip_rc(launch_sup_shift_y(pb, ea.yd, ea.psid, ea.theta, (const cd*)p->x_sup,
@@ -324,6 +375,7 @@ int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, i
                                     (const cd*)p->x_d_true, p->llf, iters, it, ea.done, p->varn_t,
                                     s))))
             return rc;
+        if (nz && (rc = noise_update(pb, p, ea.mom, ea.done, nz, nullptr, iters, it, s))) return rc;
         if (early && !fold_stop &&
             (rc = hip_rc(launch_early_stop(pb, ma.theta, (const cd*)p->h_true, done, p->iters_done,
                                            it, s))))
@@ -337,6 +389,41 @@ int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, i
             return SBCE_EHIP;
     }
     return SBCE_OK;
+}
+
+int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+            void* hip_stream) {
+    return em_run(d, p, iters, estep_mode, solve_mode, nullptr, hip_stream);
+}
+
+int sbce_em_noise(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+                  const sbce_noise_opts* o, void* hip_stream) {
+    if (!o) return SBCE_EINVAL;
+    return em_run(d, p, iters, estep_mode, solve_mode, o, hip_stream);
+}
+
+int sbce_noise_workspace_bytes(const sbce_dims* d, size_t* bytes) {
+    Problem pb;
+    if (!bytes || !make_problem(d, pb)) return SBCE_EINVAL;
+    *bytes = noise_scratch_bytes(pb);
+    return SBCE_OK;
+}
+
+int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
+                   const sbce_noise_opts* o, void* hip_stream) {
+    Problem pb;
+    if (!make_problem(d, pb) || !p || !o) return SBCE_EINVAL;
+    const void* req[] = {p->y_d, p->y_p, p->psi_d, p->u_p, p->theta, moments};
+    for (const void* q : req)
+        if (!q || !aligned16(q)) return SBCE_EINVAL;
+    if (p->varn_t && ((uintptr_t)p->varn_t & 7)) return SBCE_EINVAL;
+    if (int rc = check_noise(p, o, pb)) return rc;
+    if (pb.B == 0) return SBCE_OK;
+    clear_stale_error();
+    NoiseFinalArgs f{};
+    f.prev_t = p->varn_t; f.prev = pb.varn;
+    f.status_base = debug_nondefault() ? SBCE_STATUS_DEBUG : 0;
+    return noise_update(pb, p, (const cd*)moments, nullptr, o, &f, 1, 0, (hipStream_t)hip_stream);
 }
 
 int sbce_estep(const sbce_dims* d, const sbce_ptrs* p, int estep_mode, void* moments,

@@ -528,4 +528,35 @@ constexpr int kDetectMaxJ = 65536;
 bool detect_supported(int NT, int NR, int M);   // 1..4, 1..8, M^NT <= kDetectMaxJ
 hipError_t launch_detect(DetectArgs a, hipStream_t s);
 
+// Noise-variance update (noise.hip, sbce_noise_var / sbce_em_noise): two launches per update
+struct NoiseArgs {
+    const cd* yd;      // [B][Td][NR]
+    const cd* yp;      // [B][Tp][NR]
+    const cd* psid;    // [B][Td][P]
+    const cd* up;      // [B][Tp][L]
+    const cd* theta;   // [B][K]
+    const cd* mom;     // [B][Td][NT + NT*NT]
+    const int32_t* done;  // [B] or null: stopped trials are skipped
+    double* part;      // [B][nblk] block sums of Q (caller's scratch)
+    int NR, P, Tp, Td, nblk;   // set by launch_noise_partial
+};
+struct NoiseFinalArgs {
+    const double* part;   // [B][nblk]
+    const int32_t* done;  // [B] or null
+    double* varn_est;     // [B] out
+    const double* prev_t; // [B] the parameter before the update (may alias varn_est), or null: prev
+    double prev;
+    double* hist;         // [B][iters] or null
+    int32_t* status;      // [B] or null
+    int status_base;      // >= 0: status[b] = status_base | flag (stand-alone call); < 0: OR the flag in
+    double varn_min;
+    int iters, it;
+    int B, nblk;          // set by launch_noise_final
+    double denom;         // n_rx (T_p + T_d), set by launch_noise_final
+};
+int noise_nblk(const Problem& pb);   // blocks per trial: a function of (T_d, T_p, n_rx) only
+hipError_t launch_noise_init(int B, double* est, const double* varn_t, double varn, hipStream_t s);
+hipError_t launch_noise_partial(const Problem& pb, NoiseArgs a, hipStream_t s);
+hipError_t launch_noise_final(const Problem& pb, NoiseFinalArgs f, hipStream_t s);
+
 }  // namespace sbce

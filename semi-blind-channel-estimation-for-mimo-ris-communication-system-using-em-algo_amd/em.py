@@ -165,6 +165,120 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
     return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
 
 
+_NOISE_MODES = ("soft", "hard", "pm", "pm_soft", "zf", "mmse")
+
+
+def _noise_checks(mode, varn_min):
+    """Argument checks of the noise-estimating calls (made before the device is touched)."""
+    if mode not in _NOISE_MODES:
+        raise ValueError(f"noise estimation supports the modes {_NOISE_MODES}, not {mode!r}")
+    vmin = float(varn_min)
+    if not vmin > 0:
+        raise ValueError("varn_min must be > 0")
+    return vmin
+
+
+def _noise_scratch(torch, lib, dims):
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.sbce_noise_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
+               "sbce_noise_workspace_bytes")
+    return torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+
+
+def noise_var_batch(y_d, y_p, psi_d, u_p, theta, m, S, varn_min=1e-6, return_status=False):
+    """One noise-variance update per trial (sbce_noise_var, csrc/noise.hip) from a channel estimate
+    and posterior moments: sigma^2 = Q / (n_rx (T_p + T_d)),
+    Q = sum_p ||y_p - H_c u_p||^2 + sum_t (||y_t - H_t m_t||^2 + tr(H_t (S_t - m_t m_t^H) H_t^H)).
+    Layouts as em_batch; theta (B,K), m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx) (estep_batch's outputs).
+    Returns sigma^2 (B,) float64 [, status (B,): SBCE_STATUS_NOISE where sigma^2 < varn_min^2 and
+    varn_min^2 is returned]."""
+    vmin = _noise_checks("soft", varn_min)
+    B, T_d, n_rx = np.shape(y_d)
+    n_tx = np.shape(m)[2]
+    if np.shape(S) != (B, T_d, n_tx, n_tx) or np.shape(m) != (B, T_d, n_tx):
+        raise ValueError("noise_var_batch: m must be (B,T_d,n_tx) and S (B,T_d,n_tx,n_tx)")
+    if np.shape(u_p)[2] != np.shape(psi_d)[2] * n_tx:
+        raise ValueError("u_p width must be P*n_tx")
+    torch = _torch()
+    lib = _lib.load()
+    dims, ptrs, keep = _stage_setup(torch, y_d, y_p, psi_d, u_p, np.ones(2, dtype=complex), theta,
+                                    1.0, workspace=False)
+    mom = _dev(torch, np.concatenate([np.asarray(m).reshape(B, T_d, n_tx),
+                                      np.asarray(S).reshape(B, T_d, n_tx * n_tx)], axis=2),
+               np.complex128)
+    est = torch.zeros(B, dtype=torch.float64, device="cuda")
+    scratch = _noise_scratch(torch, lib, dims)
+    opts = _lib.NoiseOpts(est.data_ptr(), None, scratch.data_ptr(), scratch.numel(), vmin, 0)
+    _lib.check(lib.sbce_noise_var(dims, ptrs, mom.data_ptr(), opts,
+                                  torch.cuda.current_stream().cuda_stream), "sbce_noise_var")
+    torch.cuda.current_stream().synchronize()
+    v = est.cpu().numpy()
+    return (v * v, keep[7].cpu().numpy()) if return_status else v * v
+
+
+def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", solve="chol",
+                   partition_r=0, h_true=None, varn_min=1e-6, return_device=False):
+    """em_batch with the noise parameter unknown (sbce_em_noise): it is estimated per trial beside
+    theta, on the device, inside the iteration chain -- per iteration E-step, M-step, noise update
+    (csrc/noise.hip), oracle early stop.  ``varn`` (one value or (B,)) is only the START of the
+    parameter; the posterior of every E-step divides by the current estimate squared, sigma^2.
+    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse".  varn_min: floor of the parameter (a
+    trial that reaches it has SBCE_STATUS_NOISE set and varn == varn_min exactly).
+    Returns dict(theta (B,K), varn (B,) the parameter after each trial's last update, sigma2 =
+    varn**2, hist (B,itera) the parameter after each iteration (a stopped trial's later entries
+    hold its last value), status (B,), iters_done (B,)).
+    ``detect_batch(..., varn=res["varn"], noise="em")`` demaps with the estimated variance."""
+    vmin = _noise_checks(mode, varn_min)
+    if solve not in _SOLVES:
+        raise ValueError(f"unknown solve {solve!r}")
+    if int(itera) < 1:
+        raise ValueError("itera must be >= 1")
+    torch = _torch()
+    lib = _lib.load()
+
+    def dev(x):
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            return (x if x.is_cuda else x.to("cuda")).contiguous()
+        return _dev(torch, x, np.complex128)
+
+    Yd, Yp, Ps, Up, Cs = dev(y_d), dev(y_p), dev(psi_d), dev(u_p), dev(cons)
+    th = dev(theta0).clone()
+    B, T_d, n_rx = Yd.shape
+    T_p, P, L = Yp.shape[1], Ps.shape[2], Up.shape[2]
+    if L % P:
+        raise ValueError("u_p width must be P*n_tx")
+    n_tx = L // P
+    if th.shape != (B, L * n_rx):
+        raise ValueError(f"theta0 shape {tuple(th.shape)} != {(B, L * n_rx)}")
+    varn0, Vt = _varn_arg(torch, varn, B)
+    dims = _lib.Dims(B, n_tx, n_rx, P, T_p, T_d, Cs.shape[0], int(partition_r), varn0, 1.0)
+    ws = torch.empty(max(_lib.workspace_bytes(dims, _SOLVES[solve]), 16), dtype=torch.uint8,
+                     device="cuda")
+    scratch = _noise_scratch(torch, lib, dims)
+    status = torch.zeros(B, dtype=torch.int32, device="cuda")
+    iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
+    est = torch.zeros(B, dtype=torch.float64, device="cuda")
+    hist = torch.zeros((B, int(itera)), dtype=torch.float64, device="cuda")
+    Ht = dev(h_true)
+    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
+                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), th.data_ptr(), None,
+                     None, Ht.data_ptr() if Ht is not None else None, iters_done.data_ptr(),
+                     status.data_ptr(), ws.data_ptr(), ws.numel(), None, None,
+                     Vt.data_ptr() if Vt is not None else None)
+    opts = _lib.NoiseOpts(est.data_ptr(), hist.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                          vmin, 0)
+    _lib.check(lib.sbce_em_noise(dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve], opts,
+                                 torch.cuda.current_stream().cuda_stream), "sbce_em_noise")
+    out = dict(theta=th, varn=est, sigma2=est * est, hist=hist, status=status,
+               iters_done=iters_done)
+    if return_device:
+        return out
+    torch.cuda.current_stream().synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
 def _prepare_single(Y_d, Y_p, Z_p, PsiTilde_td, all_possibleSymbols, M, h_initial, n_tx=None,
                     cons=None):
     n_rx = np.asarray(Y_d[0]).shape[0]

@@ -9,6 +9,8 @@ estimator with every trial of a sweep point batched into ONE sbce_em call.
   detection_vs_snr  SER / BER / NMSE per SNR of ONE detector (sbce_detect) fed the channel of
                every estimator, the pilot-only start and the true channel, on the data of
                SNR/all_Detectors.py (gen_snr)
+  noise_est_vs_snr  NMSE per SNR of the EM with the generating noise parameter, with a fixed wrong
+               one and with the parameter estimated from the data (sbce_em_noise), on gen_snr's data
   nmse_vs_tp_superimposed  "Parallel/ParallelProtocol_Tp.py":106-136 (superimposed pilots)
   nmse_vs_tp_gaussian      "Proposed method/MIMO_Gaussian_proposed.py":158-177 (Gaussian prior)
   nmse_grid_detectors      "Proposed method/all_detectorsvsTd.py":345-405 (five EMs per T_d
@@ -35,7 +37,7 @@ import numpy as np
 from . import signal_model as sm
 from .distributed import Accumulators, shard
 from .em import (em_batch, em_approx_batch, ser_batch, gauss_expand_batch, nmse_batch,
-                 detect_batch, _GAUSS_CONS)
+                 detect_batch, em_batch_noise, _GAUSS_CONS)
 from .qam import qam_constellation, gray_labeling
 
 
@@ -251,6 +253,50 @@ def nmse_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2
         flagged = acc.extra[:, 0].reshape(nm, ns)
         return np.asarray(SNR), curves, {mode: flagged[mi] for mi, mode in enumerate(modes)}
     return np.asarray(SNR), curves
+
+
+NOISE_CURVES = ("known", "assumed", "estimated")
+
+
+def noise_est_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2, itera=8,
+                     monte_iter=15, M=4, varn_assumed=1.0, power=10.0, seed=0, replay=True,
+                     mode="soft", varh=1.0, varn_min=1e-6, batch_snr=True):
+    """What estimating the noise parameter is worth, per SNR, on gen_snr's data (the layout of
+    PMd/SNR/all_Detectors.py:362-370): the mean NMSE of the EM run with
+      'known'     the generating varn as its parameter (em_batch),
+      'assumed'   the fixed wrong parameter varn_assumed (em_batch),
+      'estimated' the parameter estimated from the data, started at varn_assumed (em_batch_noise),
+    and the mean of sigma_hat^2 / sigma_true^2 of the third (sigma_true^2 = varn, the variance the
+    noise was drawn with; sigma_hat^2 = the estimate's ``sigma2``).
+    Trials shard over ranks as in nmse_vs_snr; the SNR axis rides in one call per curve through
+    per-trial parameters (batch_snr=False: one call per point, the same results); the accumulators
+    are all-reduced ONCE.  Returns (SNR, {curve: NMSE per SNR}, ratio per SNR)."""
+    if not varn_assumed > 0:
+        raise ValueError("varn_assumed must be > 0")
+    dist, world, rank = _dist()
+    mine = shard(monte_iter, world, rank).tolist()
+    points, varns = gen_snr(SNR, T_d, T_p, N, n_rx, n_tx, monte_iter, M, power, seed, replay,
+                            varh, keep=mine)
+    cons = qam_constellation(M)
+    nc, ns = len(NOISE_CURVES), len(SNR)
+    acc = Accumulators(nc * ns, n_extra=1)
+    for ks, counts, b, vn in _snr_groups(points, varns, batch_snr):
+        args = (b["y_d"], b["y_p"], b["psi_d"], b["u_p"], cons)
+        vt = np.broadcast_to(np.asarray(vn, dtype=float), (len(b["h"]),))
+        known = em_batch(*args, vn, itera, b["theta0"], mode=mode)
+        fixed = em_batch(*args, float(varn_assumed), itera, b["theta0"], mode=mode)
+        est = em_batch_noise(*args, float(varn_assumed), itera, b["theta0"], mode=mode,
+                             varn_min=varn_min)
+        ratio = (np.asarray(est["sigma2"]) / vt)[:, None]
+        off = np.cumsum([0] + counts)
+        for ci, r in enumerate((known, fixed, est)):
+            err = _nmse(np.asarray(r["theta"]), b["h"])
+            for k, o0, o1 in zip(ks, off[:-1], off[1:]):
+                acc.add(ci * ns + k, err[o0:o1], extra_values=ratio[o0:o1] if ci == 2 else None)
+    acc.allreduce(dist)                   # the sweep's only collective
+    mean = acc.mean_nmse().reshape(nc, ns)
+    ratio = acc.mean_extra()[:, 0].reshape(nc, ns)[2]
+    return np.asarray(SNR), {c: mean[i] for i, c in enumerate(NOISE_CURVES)}, ratio
 
 
 def gen_ser(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=20, N=30, n_rx=2, n_tx=2, monte_iter=75, M=4,
