@@ -387,6 +387,67 @@ int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
 int sbce_em_noise(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode,
                   int solve_mode, const sbce_noise_opts* o, void* hip_stream);
 
+/* ---- Observed-data log-likelihood and a truth-free convergence stop (an additive extension of
+ * ABI 7: no existing struct or entry point changes).  The quantity the SOFT EM ascends, per trial
+ * b with s2 = varn_b^2 (p->varn_t[b], or d->varn), J = M^n_tx and d_j = ||y_t - H_t x_j||^2 over
+ * the hypotheses in itertools.product order, H_t being the channel of the detector above:
+ *   ll_sym[b][t] = -d_min/s2 + log sum_j e^{-(d_j - d_min)/s2} - log J - n_rx log(pi s2)
+ *   ll[b]        = sum_t ll_sym[b][t] + sum_pilots ( -||y_p - H_c u_p||^2/s2 - n_rx log(pi s2) )
+ * (the pilot term is empty when t_p = 0).  The minimum-shifted sum has a term equal to 1, so
+ * every output is finite for any s2 > 0.  No floating-point atomic is used and every reduction
+ * order is fixed by the shape alone: a trial's bits do not depend on the batch around it. */
+
+/* Device scratch of the log-likelihood call for `d`. */
+int sbce_loglik_workspace_bytes(const sbce_dims* d, size_t* bytes);
+
+/* ll [B] (and ll_sym [B][T_d] when not NULL) of every trial from p->theta, which is read and
+ * never written: two kernel launches on `hip_stream`, no memset, no allocation, no
+ * synchronisation; capturable in a HIP graph as a linear chain.  Uses p->y_d, y_p, psi_d, u_p,
+ * cons, theta and varn_t; p->workspace, llf, h_true and status are not used.  Decided before any
+ * HIP call -- SBCE_EINVAL: bad dims (varn <= 0 among them), a null or misaligned required
+ * pointer (16 bytes complex, 8 bytes float64: ll, ll_sym, varn_t, scratch), p->x_sup set;
+ * SBCE_EUNSUPPORTED: n_tx > 4, n_rx > 8, m not a power of two in 2..64 or m^n_tx > 65536 (the
+ * detector's limits); SBCE_EWORKSPACE: scratch_bytes too small. */
+int sbce_loglik(const sbce_dims* d, const sbce_ptrs* p, double* ll, double* ll_sym, void* scratch,
+                size_t scratch_bytes, void* hip_stream);
+
+#define SBCE_STATUS_CONVERGED 128   /* the trial stopped by a rule of sbce_conv_opts */
+
+typedef struct sbce_conv_opts {
+    double tol_theta;     /* >= 0: stop when ||theta_l - theta_{l-1}||^2 <= tol_theta^2 ||theta_l||^2
+                             (theta_{-1} is the caller's h_initial; 0 stops at an exact fixed point) */
+    double tol_ll;        /* >= 0; > 0 requires ll_hist: stop when l >= 1 and
+                             ll_l - ll_{l-1} <= tol_ll |ll_l|; 0 switches the rule off */
+    int32_t min_iters;    /* >= 1: no stop before this many iterations were performed */
+    int32_t flags;        /* 0 */
+    double* dtheta_hist;  /* may be NULL: [B][iters] sqrt(||dtheta||^2 / ||theta_l||^2) after each
+                             iteration */
+    double* ll_hist;      /* may be NULL: [B][iters] ll after each iteration (costs one log-likelihood
+                             pass per iteration) */
+    void* scratch;        /* device scratch, 16-byte aligned */
+    size_t scratch_bytes; /* at least sbce_conv_workspace_bytes */
+} sbce_conv_opts;
+
+/* Device scratch of the convergence stop for `d`; want_ll != 0 when ll_hist is set. */
+int sbce_conv_workspace_bytes(const sbce_dims* d, int want_ll, size_t* bytes);
+
+/* The EM chain with a per-trial stop that needs no ground truth.  nz == NULL: the iterations of
+ * sbce_em; nz set: those of sbce_em_noise.  Per iteration l: E-step, M-step, noise update (nz),
+ * log-likelihood at the new theta and the current noise parameter (ll_hist), then one launch that
+ * forms both norms in a fixed order, writes the histories and decides.  A trial that stops gets
+ * SBCE_STATUS_CONVERGED and iters_done = l + 1 and is masked from then on exactly as an
+ * oracle-stopped trial; its later history entries (varn_hist too) keep their last value.  The
+ * decision has no division and a NaN never stops a trial.  While no trial can stop (min_iters =
+ * iters) theta is bitwise the plain chain's.  Launches per iteration beside the chain's own: one,
+ * or three with ll_hist.  Decided before any HIP call, beside the chain's own checks --
+ * SBCE_EINVAL: cv NULL, p->h_true, p->llf or p->x_sup set (the point is to need no truth), a
+ * negative or NaN tolerance, tol_ll > 0 without ll_hist, min_iters < 1, flags != 0, a misaligned
+ * history (8 bytes) or a null or misaligned scratch (16 bytes); SBCE_EUNSUPPORTED:
+ * SBCE_ESTEP_GAUSS, or ll_hist beyond the log-likelihood's limits; SBCE_EWORKSPACE.  The theta
+ * rule works in every other E-step mode, PM at n_tx = 8 included. */
+int sbce_em_conv(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+                 const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ SBCE_STATUS_DEBUG = 8
 SBCE_STATUS_RANK = 16
 SBCE_STATUS_SINGULAR = 32
 SBCE_STATUS_NOISE = 64
+SBCE_STATUS_CONVERGED = 128
 SBCE_DETECT_MAXLOG = 1
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
@@ -39,7 +40,9 @@ EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_estep", "sbce_mstep", "sbce_ser", "sbce_gauss_expand", "sbce_nmse",
             "sbce_approx_workspace_bytes", "sbce_approx_em",
             "sbce_detect_workspace_bytes", "sbce_detect",
-            "sbce_noise_workspace_bytes", "sbce_noise_var", "sbce_em_noise")
+            "sbce_noise_workspace_bytes", "sbce_noise_var", "sbce_em_noise",
+            "sbce_loglik_workspace_bytes", "sbce_loglik", "sbce_conv_workspace_bytes",
+            "sbce_em_conv")
 
 
 class SbceUnavailable(RuntimeError):
@@ -102,6 +105,14 @@ class NoiseOpts(ctypes.Structure):
     _fields_ = [("varn_est", ctypes.c_void_p), ("varn_hist", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
                 ("varn_min", ctypes.c_double), ("flags", ctypes.c_int32)]
+
+
+class ConvOpts(ctypes.Structure):
+    """sbce_conv_opts (include/sbce.h): the truth-free convergence stop of sbce_em_conv."""
+    _fields_ = [("tol_theta", ctypes.c_double), ("tol_ll", ctypes.c_double),
+                ("min_iters", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("dtheta_hist", ctypes.c_void_p), ("ll_hist", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
 
 
 _lib = None
@@ -176,6 +187,18 @@ def load(path=None):
     lib.sbce_em_noise.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
                                   ctypes.c_int, ctypes.c_int, ctypes.POINTER(NoiseOpts),
                                   ctypes.c_void_p]
+    lib.sbce_loglik_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_loglik_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_loglik.restype = ctypes.c_int
+    lib.sbce_loglik.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.sbce_conv_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_conv_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_em_conv.restype = ctypes.c_int
+    lib.sbce_em_conv.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
+                                 ctypes.c_int, ctypes.c_int, ctypes.POINTER(NoiseOpts),
+                                 ctypes.POINTER(ConvOpts), ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

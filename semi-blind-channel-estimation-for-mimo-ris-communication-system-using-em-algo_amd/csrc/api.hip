@@ -240,6 +240,48 @@ int noise_update(const Problem& pb, const sbce_ptrs* p, const cd* mom, const int
     return hip_rc(launch_noise_final(pb, f, s));
 }
 
+// the log-likelihood's scratch: per-symbol terms (used when the caller takes no ll_sym), then the
+// pilot block sums
+size_t loglik_sym_bytes(const Problem& pb) {
+    return align_up((size_t)pb.B * pb.Td * sizeof(double));
+}
+size_t loglik_scratch_bytes(const Problem& pb) {
+    return loglik_sym_bytes(pb) + align_up((size_t)pb.B * loglik_npb(pb) * sizeof(double));
+}
+
+LoglikArgs loglik_args(const Problem& pb, const sbce_ptrs* p, double* ll, double* ll_sym,
+                       char* scratch) {
+    LoglikArgs a{};
+    a.yd = (const cd*)p->y_d; a.yp = (const cd*)p->y_p; a.psid = (const cd*)p->psi_d;
+    a.up = (const cd*)p->u_p; a.cons = (const cd*)p->cons; a.theta = (const cd*)p->theta;
+    a.varn_t = p->varn_t;
+    a.sym = ll_sym ? ll_sym : (double*)scratch;
+    a.ppart = (double*)(scratch + loglik_sym_bytes(pb));
+    a.ll = ll;
+    return a;
+}
+
+// the convergence stop's scratch: theta_prev, the iteration's ll, then the log-likelihood's own
+size_t conv_prev_bytes(const Problem& pb) { return align_up((size_t)pb.B * pb.K * sizeof(cd)); }
+size_t conv_ll_bytes(const Problem& pb) { return align_up((size_t)pb.B * sizeof(double)); }
+size_t conv_scratch_bytes(const Problem& pb, bool want_ll) {
+    return conv_prev_bytes(pb) + conv_ll_bytes(pb) + (want_ll ? loglik_scratch_bytes(pb) : 0);
+}
+
+// sbce_conv_opts against `pb` (sbce_em_conv): decided before any HIP call
+int check_conv(const sbce_ptrs* p, const sbce_conv_opts* cv, const Problem& pb) {
+    if (!p || !cv) return SBCE_EINVAL;
+    if (p->h_true || p->llf || p->x_sup) return SBCE_EINVAL;
+    if (!(cv->tol_theta >= 0.0) || !(cv->tol_ll >= 0.0) || cv->min_iters < 1 || cv->flags != 0)
+        return SBCE_EINVAL;
+    if (cv->tol_ll > 0.0 && !cv->ll_hist) return SBCE_EINVAL;
+    if (((uintptr_t)cv->dtheta_hist & 7) || ((uintptr_t)cv->ll_hist & 7)) return SBCE_EINVAL;
+    if (!cv->scratch || !aligned16(cv->scratch)) return SBCE_EINVAL;
+    if (cv->ll_hist && !loglik_supported(pb)) return SBCE_EUNSUPPORTED;
+    if (cv->scratch_bytes < conv_scratch_bytes(pb, cv->ll_hist != nullptr)) return SBCE_EWORKSPACE;
+    return SBCE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,15 +316,17 @@ int sbce_workspace_bytes_solve(const sbce_dims* d, int solve_mode, size_t* bytes
     return SBCE_OK;
 }
 
-// The EM loop of sbce_em and sbce_em_noise.  nz == nullptr: sbce_em.  nz: the noise parameter is
-// estimated (noise.hip): nz->varn_est is the E-step's per-trial parameter, updated after every
-// M-step, and the oracle early stop runs after the update in its own launch.
+// The EM loop of sbce_em, sbce_em_noise and sbce_em_conv.  nz == nullptr: sbce_em.  nz: the noise
+// parameter is estimated (noise.hip): nz->varn_est is the E-step's per-trial parameter, updated
+// after every M-step, and the oracle early stop runs after the update in its own launch.  cv: the
+// truth-free stop (loglik.hip) closes every iteration and owns the `done` flags; with cv absent
+// the launches are exactly those of the loop without it.
 static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
-                  const sbce_noise_opts* nz, void* hip_stream) {
+                  const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream) {
     clear_stale_error();
     Problem pb;
     if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
-    if (nz && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
+    if ((nz || cv) && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
     if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
     if (solve_mode != SBCE_SOLVE_CHOL && solve_mode != SBCE_SOLVE_CHOL_DROP &&
         solve_mode != SBCE_SOLVE_MINNORM)
@@ -299,6 +343,7 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
                      !aligned16(p->x_sup)))
         return SBCE_EINVAL;
     if (nz && (rc = check_noise(p, nz, pb))) return rc;
+    if (cv && (rc = check_conv(p, cv, pb))) return rc;
     if (pb.B == 0 || iters == 0) return SBCE_OK;
     hipStream_t s = (hipStream_t)hip_stream;
     const Carve c = carve(pb, solve_mode);
@@ -317,7 +362,7 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
 
     EstepArgs ea;
     ea.yd = (const cd*)p->y_d; ea.psid = (const cd*)p->psi_d; ea.theta = (const cd*)p->theta;
-    ea.cons = (const cd*)p->cons; ea.mom = (cd*)(ws + c.mom); ea.done = early ? done : nullptr;
+    ea.cons = (const cd*)p->cons; ea.mom = (cd*)(ws + c.mom); ea.done = (early || cv) ? done : nullptr;
     ea.status = p->status;
     ea.varn_t = p->varn_t;
     if (nz) {                                // the estimate starts at the caller's parameter
@@ -342,6 +387,23 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
     // the LLF kernel reads theta before the stop decision of the same iteration: no fold with it
     // nor with the noise update, which follows a trial's last M-step
     const bool fold_stop = small2 && early && !p->llf && !nz;
+    ConvArgs ca{};
+    LoglikArgs la{};
+    if (cv) {                                // theta_{-1} is the caller's h_initial
+        char* cs = (char*)cv->scratch;
+        double* ll_cur = (double*)(cs + conv_prev_bytes(pb));
+        ca.theta = ma.theta; ca.prev = (cd*)cs; ca.ll_cur = ll_cur;
+        ca.dth_hist = cv->dtheta_hist; ca.ll_hist = cv->ll_hist; ca.done = done;
+        ca.iters_done = p->iters_done; ca.status = p->status;
+        ca.tol_theta2 = cv->tol_theta * cv->tol_theta; ca.tol_ll = cv->tol_ll;
+        ca.min_iters = cv->min_iters; ca.iters = iters;
+        if (cv->ll_hist) {
+            la = loglik_args(pb, p, ll_cur, nullptr, cs + conv_prev_bytes(pb) + conv_ll_bytes(pb));
+            la.varn_t = ea.varn_t;           // the current parameter (the estimate, with nz)
+            la.done = done;
+        }
+        if ((rc = hip_rc(launch_conv_init(pb, ma.theta, ca.prev, s)))) return rc;
+    }
     for (int it = 0; it < iters; ++it) {
         if (p->x_sup) {
             if ((rc = hip_rc(launch_sup_shift_y(pb, ea.yd, ea.psid, ea.theta, (const cd*)p->x_sup,
@@ -380,9 +442,14 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
             (rc = hip_rc(launch_early_stop(pb, ma.theta, (const cd*)p->h_true, done, p->iters_done,
                                            it, s))))
             return rc;
+        if (cv) {
+            if (cv->ll_hist && (rc = hip_rc(launch_loglik(pb, la, s)))) return rc;
+            ca.it = it;
+            if ((rc = hip_rc(launch_conv_step(pb, ca, s)))) return rc;
+        }
     }
     if (p->x_dest && (rc = hip_rc(launch_decisions(pb, ea.mom, (cd*)p->x_dest, s)))) return rc;
-    if (!early && p->iters_done) {
+    if (!early && !cv && p->iters_done) {
         // every trial ran all iterations: fill with `iters` via a tiny host-free memset pattern
         // (int32 fill is done on device by hipMemsetD32Async)
         if (hipMemsetD32Async((hipDeviceptr_t)p->iters_done, iters, (size_t)pb.B, s) != hipSuccess)
@@ -393,13 +460,50 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
 
 int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
             void* hip_stream) {
-    return em_run(d, p, iters, estep_mode, solve_mode, nullptr, hip_stream);
+    return em_run(d, p, iters, estep_mode, solve_mode, nullptr, nullptr, hip_stream);
 }
 
 int sbce_em_noise(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
                   const sbce_noise_opts* o, void* hip_stream) {
     if (!o) return SBCE_EINVAL;
-    return em_run(d, p, iters, estep_mode, solve_mode, o, hip_stream);
+    return em_run(d, p, iters, estep_mode, solve_mode, o, nullptr, hip_stream);
+}
+
+int sbce_conv_workspace_bytes(const sbce_dims* d, int want_ll, size_t* bytes) {
+    Problem pb;
+    if (!bytes || !make_problem(d, pb)) return SBCE_EINVAL;
+    *bytes = conv_scratch_bytes(pb, want_ll != 0);
+    return SBCE_OK;
+}
+
+int sbce_em_conv(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+                 const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream) {
+    if (!cv) return SBCE_EINVAL;
+    return em_run(d, p, iters, estep_mode, solve_mode, nz, cv, hip_stream);
+}
+
+int sbce_loglik_workspace_bytes(const sbce_dims* d, size_t* bytes) {
+    Problem pb;
+    if (!bytes || !make_problem(d, pb)) return SBCE_EINVAL;
+    *bytes = loglik_scratch_bytes(pb);
+    return SBCE_OK;
+}
+
+int sbce_loglik(const sbce_dims* d, const sbce_ptrs* p, double* ll, double* ll_sym, void* scratch,
+                size_t scratch_bytes, void* hip_stream) {
+    Problem pb;
+    if (!make_problem(d, pb)) return SBCE_EINVAL;
+    int rc = check_ptrs(p, pb, false);
+    if (rc) return rc;
+    if (p->x_sup) return SBCE_EINVAL;
+    if (!ll || ((uintptr_t)ll & 7) || ((uintptr_t)ll_sym & 7)) return SBCE_EINVAL;
+    if (!scratch || ((uintptr_t)scratch & 7)) return SBCE_EINVAL;
+    if (!loglik_supported(pb)) return SBCE_EUNSUPPORTED;
+    if (scratch_bytes < loglik_scratch_bytes(pb)) return SBCE_EWORKSPACE;
+    if (pb.B == 0) return SBCE_OK;
+    clear_stale_error();
+    return hip_rc(launch_loglik(pb, loglik_args(pb, p, ll, ll_sym, (char*)scratch),
+                                (hipStream_t)hip_stream));
 }
 
 int sbce_noise_workspace_bytes(const sbce_dims* d, size_t* bytes) {

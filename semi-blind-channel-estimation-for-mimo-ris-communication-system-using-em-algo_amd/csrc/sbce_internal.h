@@ -559,4 +559,44 @@ hipError_t launch_noise_init(int B, double* est, const double* varn_t, double va
 hipError_t launch_noise_partial(const Problem& pb, NoiseArgs a, hipStream_t s);
 hipError_t launch_noise_final(const Problem& pb, NoiseFinalArgs f, hipStream_t s);
 
+// Observed-data log-likelihood (loglik.hip, sbce_loglik): two launches per call
+struct LoglikArgs {
+    const cd* yd;      // [B][Td][NR]
+    const cd* yp;      // [B][Tp][NR]
+    const cd* psid;    // [B][Td][P]
+    const cd* up;      // [B][Tp][L]
+    const cd* cons;    // [M]
+    const cd* theta;   // [B][K]
+    const double* varn_t;   // [B] or null
+    const int32_t* done;    // [B] or null: stopped trials are skipped (ll[b] is left as it is)
+    double* sym;       // [B][Td] per-symbol log-evidence (the caller's ll_sym, or scratch)
+    double* ppart;     // [B][npb] block sums of the pilot residuals (scratch)
+    double* ll;        // [B]
+    int B, NT, NR, P, Tp, Td, M, lgM;   // set by launch_loglik, as the next two lines
+    int TC, chunks;    // symbols per workgroup, symbol workgroups per trial
+    int npb;           // pilot workgroups per trial
+    double varn;
+};
+bool loglik_supported(const Problem& pb);   // detect_supported's limits, M a power of two
+int loglik_npb(const Problem& pb);          // a function of (T_p, n_rx) only
+hipError_t launch_loglik(const Problem& pb, LoglikArgs a, hipStream_t s);
+
+// Truth-free convergence stop (loglik.hip, sbce_em_conv): one launch per iteration
+struct ConvArgs {
+    const cd* theta;   // [B][K]
+    cd* prev;          // [B][K] theta after the previous iteration (h_initial before the first)
+    const double* ll_cur;   // [B] this iteration's log-likelihood (read when ll_hist is set)
+    double* dth_hist;  // [B][iters] or null
+    double* ll_hist;   // [B][iters] or null
+    int32_t* done;     // [B]
+    int32_t* iters_done;    // [B] or null
+    int32_t* status;   // [B] or null
+    double tol_theta2; // tol_theta^2
+    double tol_ll;
+    int min_iters, iters, it;
+    int K;             // set by launch_conv_step
+};
+hipError_t launch_conv_init(const Problem& pb, const cd* theta, cd* prev, hipStream_t s);
+hipError_t launch_conv_step(const Problem& pb, ConvArgs c, hipStream_t s);
+
 }  // namespace sbce

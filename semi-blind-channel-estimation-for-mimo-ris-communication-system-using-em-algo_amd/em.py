@@ -279,6 +279,129 @@ def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft",
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
+def _scratch(torch, query, what, *args):
+    """A device scratch buffer of the size a sbce_*_workspace_bytes entry point reports."""
+    nb = ctypes.c_size_t(0)
+    _lib.check(query(*args, ctypes.byref(nb)), what)
+    return torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+
+
+def loglik_batch(y_d, y_p, psi_d, u_p, cons, theta, varn, n_tx, per_symbol=False):
+    """Observed-data log-likelihood of every trial (sbce_loglik, csrc/loglik.hip) at a channel
+    estimate theta (B,K) and the noise parameter varn (one value or (B,); sigma^2 = varn**2, the
+    E-step's denominator) under uniform symbols: the pilots' Gaussian terms plus, per data symbol,
+    log (1/J) sum_j CN(y_t; H_t x_j, sigma^2 I) over the J = M**n_tx hypotheses -- the quantity
+    the soft EM ascends.  Layouts as em_batch; needs no ground truth.
+    Returns ll (B,) float64 [, ll_sym (B,T_d): the data symbols' terms]."""
+    if np.shape(u_p)[2] != np.shape(psi_d)[2] * int(n_tx):
+        raise ValueError("u_p width must be P*n_tx")
+    torch = _torch()
+    lib = _lib.load()
+    Yd, Yp, Ps, Up, Cs, Th = (_dev(torch, x, np.complex128)
+                              for x in (y_d, y_p, psi_d, u_p, cons, theta))
+    B, T_d, n_rx = Yd.shape
+    T_p, P = Yp.shape[1], Ps.shape[2]
+    if Th.shape != (B, P * int(n_tx) * n_rx):
+        raise ValueError(f"theta shape {tuple(Th.shape)} != {(B, P * int(n_tx) * n_rx)}")
+    varn0, Vt = _varn_arg(torch, varn, B)
+    dims = _lib.Dims(B, int(n_tx), n_rx, P, T_p, T_d, Cs.shape[0], 0, varn0, 1.0)
+    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
+                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), Th.data_ptr(), None,
+                     None, None, None, None, None, 0, None, None,
+                     Vt.data_ptr() if Vt is not None else None)
+    ll = torch.zeros(B, dtype=torch.float64, device="cuda")
+    sym = torch.zeros((B, T_d), dtype=torch.float64, device="cuda") if per_symbol else None
+    scratch = _scratch(torch, lib.sbce_loglik_workspace_bytes, "sbce_loglik_workspace_bytes",
+                       ctypes.byref(dims))
+    _lib.check(lib.sbce_loglik(dims, ptrs, ll.data_ptr(), sym.data_ptr() if per_symbol else None,
+                               scratch.data_ptr(), scratch.numel(),
+                               torch.cuda.current_stream().cuda_stream), "sbce_loglik")
+    torch.cuda.current_stream().synchronize()
+    return (ll.cpu().numpy(), sym.cpu().numpy()) if per_symbol else ll.cpu().numpy()
+
+
+def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta=1e-6, tol_ll=0.0,
+                  min_iters=2, estimate_noise=False, varn_min=1e-6, loglik=False, mode="soft",
+                  partition_r=0, solve="chol", return_device=False):
+    """em_batch with a per-trial stop that needs no ground truth (sbce_em_conv): a trial stops
+    after iteration l (at least min_iters performed) when ||theta_l - theta_{l-1}|| <= tol_theta
+    ||theta_l|| (theta_{-1} = theta0), or -- tol_ll > 0, which needs loglik=True -- when its
+    observed-data log-likelihood rose by at most tol_ll |ll_l|.  A stopped trial is frozen and
+    skipped by every later launch.  estimate_noise: the noise parameter is estimated beside theta
+    as in em_batch_noise (``varn`` is then only its start).  loglik=True records the
+    log-likelihood after every iteration (one sbce_loglik pass each: a diagnostic, soft-EM shapes
+    with n_tx <= 4 and M**n_tx <= 65536 only).
+    Returns dict(theta (B,K), iters_done (B,), status (B,) with SBCE_STATUS_CONVERGED where a rule
+    stopped the trial, dtheta_hist (B,max_iters) the relative step after each iteration, ll_hist
+    (B,max_iters) or None, varn (B,) the parameter each trial ended with, sigma2 = varn**2, hist
+    (B,max_iters) the parameter's history or None); a stopped trial's later history entries hold
+    its last value."""
+    if mode not in _NOISE_MODES:
+        raise ValueError(f"the convergence stop supports the modes {_NOISE_MODES}, not {mode!r}")
+    if solve not in _SOLVES:
+        raise ValueError(f"unknown solve {solve!r}")
+    iters, mi = int(max_iters), int(min_iters)
+    if iters < 1 or mi < 1:
+        raise ValueError("max_iters and min_iters must be >= 1")
+    tt, tl = float(tol_theta), float(tol_ll)
+    if not tt >= 0 or not tl >= 0:
+        raise ValueError("tol_theta and tol_ll must be >= 0")
+    if tl > 0 and not loglik:
+        raise ValueError("tol_ll > 0 needs loglik=True")
+    vmin = _noise_checks(mode, varn_min)
+    torch = _torch()
+    lib = _lib.load()
+
+    def dev(x):
+        if isinstance(x, torch.Tensor):
+            return (x if x.is_cuda else x.to("cuda")).contiguous()
+        return _dev(torch, x, np.complex128)
+
+    Yd, Yp, Ps, Up, Cs = dev(y_d), dev(y_p), dev(psi_d), dev(u_p), dev(cons)
+    th = dev(theta0).clone()
+    B, T_d, n_rx = Yd.shape
+    T_p, P, L = Yp.shape[1], Ps.shape[2], Up.shape[2]
+    if L % P:
+        raise ValueError("u_p width must be P*n_tx")
+    n_tx = L // P
+    if th.shape != (B, L * n_rx):
+        raise ValueError(f"theta0 shape {tuple(th.shape)} != {(B, L * n_rx)}")
+    varn0, Vt = _varn_arg(torch, varn, B)
+    dims = _lib.Dims(B, n_tx, n_rx, P, T_p, T_d, Cs.shape[0], int(partition_r), varn0, 1.0)
+    ws = torch.empty(max(_lib.workspace_bytes(dims, _SOLVES[solve]), 16), dtype=torch.uint8,
+                     device="cuda")
+    status = torch.zeros(B, dtype=torch.int32, device="cuda")
+    iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
+    dth = torch.zeros((B, iters), dtype=torch.float64, device="cuda")
+    llh = torch.zeros((B, iters), dtype=torch.float64, device="cuda") if loglik else None
+    cscratch = _scratch(torch, lib.sbce_conv_workspace_bytes, "sbce_conv_workspace_bytes",
+                        ctypes.byref(dims), 1 if loglik else 0)
+    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
+                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), th.data_ptr(), None,
+                     None, None, iters_done.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                     ws.numel(), None, None, Vt.data_ptr() if Vt is not None else None)
+    cv = _lib.ConvOpts(tt, tl, mi, 0, dth.data_ptr(), llh.data_ptr() if loglik else None,
+                       cscratch.data_ptr(), cscratch.numel())
+    nz, est, hist = None, None, None
+    if estimate_noise:
+        nscratch = _noise_scratch(torch, lib, dims)
+        est = torch.zeros(B, dtype=torch.float64, device="cuda")
+        hist = torch.zeros((B, iters), dtype=torch.float64, device="cuda")
+        nz = _lib.NoiseOpts(est.data_ptr(), hist.data_ptr(), nscratch.data_ptr(), nscratch.numel(),
+                            vmin, 0)
+    else:
+        est = Vt if Vt is not None else torch.full((B,), varn0, dtype=torch.float64, device="cuda")
+    _lib.check(lib.sbce_em_conv(dims, ptrs, iters, _MODES[mode], _SOLVES[solve],
+                                ctypes.byref(nz) if nz is not None else None, ctypes.byref(cv),
+                                torch.cuda.current_stream().cuda_stream), "sbce_em_conv")
+    out = dict(theta=th, iters_done=iters_done, status=status, dtheta_hist=dth, ll_hist=llh,
+               varn=est, sigma2=est * est, hist=hist)
+    if return_device:
+        return out
+    torch.cuda.current_stream().synchronize()
+    return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+
+
 def _prepare_single(Y_d, Y_p, Z_p, PsiTilde_td, all_possibleSymbols, M, h_initial, n_tx=None,
                     cons=None):
     n_rx = np.asarray(Y_d[0]).shape[0]

@@ -11,6 +11,8 @@ estimator with every trial of a sweep point batched into ONE sbce_em call.
                SNR/all_Detectors.py (gen_snr)
   noise_est_vs_snr  NMSE per SNR of the EM with the generating noise parameter, with a fixed wrong
                one and with the parameter estimated from the data (sbce_em_noise), on gen_snr's data
+  convergence_vs_snr  NMSE and iterations performed per SNR of a fixed iteration count, the
+               truth-free stop (sbce_em_conv) and the oracle stop, on gen_snr's data
   nmse_vs_tp_superimposed  "Parallel/ParallelProtocol_Tp.py":106-136 (superimposed pilots)
   nmse_vs_tp_gaussian      "Proposed method/MIMO_Gaussian_proposed.py":158-177 (Gaussian prior)
   nmse_grid_detectors      "Proposed method/all_detectorsvsTd.py":345-405 (five EMs per T_d
@@ -37,7 +39,7 @@ import numpy as np
 from . import signal_model as sm
 from .distributed import Accumulators, shard
 from .em import (em_batch, em_approx_batch, ser_batch, gauss_expand_batch, nmse_batch,
-                 detect_batch, em_batch_noise, _GAUSS_CONS)
+                 detect_batch, em_batch_noise, em_batch_conv, _GAUSS_CONS)
 from .qam import qam_constellation, gray_labeling
 
 
@@ -297,6 +299,47 @@ def noise_est_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n
     mean = acc.mean_nmse().reshape(nc, ns)
     ratio = acc.mean_extra()[:, 0].reshape(nc, ns)[2]
     return np.asarray(SNR), {c: mean[i] for i, c in enumerate(NOISE_CURVES)}, ratio
+
+
+CONV_ARMS = ("fixed", "stop", "oracle")
+
+
+def convergence_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2, itera=20,
+                       monte_iter=15, M=4, tol_theta=1e-6, min_iters=2, power=10.0, seed=0,
+                       replay=True, mode="soft", varh=1.0, batch_snr=True):
+    """What a stop rule costs and saves, per SNR, on gen_snr's data: the mean NMSE and the mean
+    number of iterations performed of the EM run with
+      'fixed'   the fixed count itera (em_batch),
+      'stop'    the truth-free stop ||theta_l - theta_{l-1}|| <= tol_theta ||theta_l||, at most
+                itera iterations (em_batch_conv),
+      'oracle'  the reference's oracle stop | ||theta|| - ||h|| | < 1 on the true channel
+                (em_batch with h_true, PM.py:110-112), at most itera iterations.
+    Trials shard over ranks as in nmse_vs_snr; the SNR axis rides in one call per arm through
+    per-trial parameters (batch_snr=False: one call per point, the same results); the accumulators
+    are all-reduced ONCE.  Returns (SNR, {arm: NMSE per SNR}, {arm: mean iterations per SNR})."""
+    dist, world, rank = _dist()
+    mine = shard(monte_iter, world, rank).tolist()
+    points, varns = gen_snr(SNR, T_d, T_p, N, n_rx, n_tx, monte_iter, M, power, seed, replay,
+                            varh, keep=mine)
+    cons = qam_constellation(M)
+    na, ns = len(CONV_ARMS), len(SNR)
+    acc = Accumulators(na * ns, n_extra=1)
+    for ks, counts, b, vn in _snr_groups(points, varns, batch_snr):
+        args = (b["y_d"], b["y_p"], b["psi_d"], b["u_p"], cons, vn, itera, b["theta0"])
+        runs = (em_batch(*args, mode=mode),
+                em_batch_conv(*args, tol_theta=tol_theta, min_iters=min_iters, mode=mode),
+                em_batch(*args, mode=mode, h_true=b["h"]))
+        off = np.cumsum([0] + counts)
+        for ai, r in enumerate(runs):
+            err = _nmse(np.asarray(r["theta"]), b["h"])
+            its = np.asarray(r["iters_done"], dtype=float)[:, None]
+            for k, o0, o1 in zip(ks, off[:-1], off[1:]):
+                acc.add(ai * ns + k, err[o0:o1], extra_values=its[o0:o1])
+    acc.allreduce(dist)                   # the sweep's only collective
+    mean = acc.mean_nmse().reshape(na, ns)
+    its = acc.mean_extra()[:, 0].reshape(na, ns)
+    return (np.asarray(SNR), {a: mean[i] for i, a in enumerate(CONV_ARMS)},
+            {a: its[i] for i, a in enumerate(CONV_ARMS)})
 
 
 def gen_ser(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=20, N=30, n_rx=2, n_tx=2, monte_iter=75, M=4,
