@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "sbce_internal.h"
 
 using namespace sbce;
@@ -176,6 +178,45 @@ void set_large(MstepArgs& ma, char* ws, const Carve& c) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// every pointer of the list is non-null and 16-byte aligned
+bool required(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs)
+        if (!q || !aligned16(q)) return false;
+    return true;
+}
+
+bool valid_solve(int mode) {
+    return mode == SBCE_SOLVE_CHOL || mode == SBCE_SOLVE_CHOL_DROP || mode == SBCE_SOLVE_MINNORM;
+}
+
+// The M-step's arguments from the caller's buffers, the given moments and the workspace carved
+// by `c` (for `solve`); no status gate (done) -- em_run sets its own.
+MstepArgs mstep_args(const Problem& pb, const sbce_ptrs* p, const void* moments, char* ws,
+                     const Carve& c, int solve) {
+    MstepArgs ma;
+    ma.yd = (const cd*)p->y_d; ma.yp = (const cd*)p->y_p; ma.psid = (const cd*)p->psi_d;
+    ma.up = (const cd*)p->u_p; ma.mom = (const cd*)moments; ma.R = (cd*)(ws + c.R);
+    ma.rhs = (cd*)(ws + c.rhs); ma.theta = (cd*)p->theta; ma.status = p->status; ma.done = nullptr;
+    ma.solve_mode = solve; ma.nbatch = pb.B;
+    set_large(ma, ws, c);
+    return ma;
+}
+
+// The E-step's arguments: moments out, and the MFMA sweep's regions of the workspace carved by
+// `c` (null: no workspace, the sweep kernel prepares each symbol itself).
+EstepArgs estep_args(const sbce_ptrs* p, void* moments, char* ws, const Carve* c) {
+    EstepArgs ea;
+    ea.yd = (const cd*)p->y_d; ea.psid = (const cd*)p->psi_d; ea.theta = (const cd*)p->theta;
+    ea.cons = (const cd*)p->cons; ea.mom = (cd*)moments; ea.done = nullptr;
+    ea.status = p->status;
+    ea.varn_t = p->varn_t;
+    const bool prep = c && c->has_prep;
+    ea.prep = prep ? (double*)(ws + c->prep) : nullptr;
+    ea.list = prep ? (int32_t*)(ws + c->list) : nullptr;
+    ea.tree = prep ? (double*)(ws + c->tree) : nullptr;
+    return ea;
+}
+
 // per-trial status starts at 0, or at SBCE_STATUS_DEBUG while a result-affecting debug switch
 // (DebugConfig) is active
 int status_init(int32_t* status, int B, hipStream_t s) {
@@ -187,10 +228,7 @@ int status_init(int32_t* status, int B, hipStream_t s) {
 
 int check_ptrs(const sbce_ptrs* p, const Problem& pb, bool need_ws, int solve = kAnySolve) {
     if (!p) return SBCE_EINVAL;
-    const void* req[] = {p->y_d, p->y_p, p->psi_d, p->u_p, p->cons, p->theta};
-    for (const void* q : req)
-        if (!q || !aligned16(q)) return SBCE_EINVAL;
-    if (pb.Tp == 0) { /* pilots optional */ }
+    if (!required({p->y_d, p->y_p, p->psi_d, p->u_p, p->cons, p->theta})) return SBCE_EINVAL;
     if (p->varn_t && ((uintptr_t)p->varn_t & 7)) return SBCE_EINVAL;
     if (need_ws) {
         if (!p->workspace || !aligned16(p->workspace)) return SBCE_EINVAL;
@@ -308,10 +346,7 @@ int sbce_workspace_bytes(const sbce_dims* d, size_t* bytes) {
 
 int sbce_workspace_bytes_solve(const sbce_dims* d, int solve_mode, size_t* bytes) {
     Problem pb;
-    if (!bytes || !make_problem(d, pb)) return SBCE_EINVAL;
-    if (solve_mode != SBCE_SOLVE_CHOL && solve_mode != SBCE_SOLVE_CHOL_DROP &&
-        solve_mode != SBCE_SOLVE_MINNORM)
-        return SBCE_EINVAL;
+    if (!bytes || !make_problem(d, pb) || !valid_solve(solve_mode)) return SBCE_EINVAL;
     *bytes = carve(pb, solve_mode).total;
     return SBCE_OK;
 }
@@ -328,9 +363,7 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
     if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
     if ((nz || cv) && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
     if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
-    if (solve_mode != SBCE_SOLVE_CHOL && solve_mode != SBCE_SOLVE_CHOL_DROP &&
-        solve_mode != SBCE_SOLVE_MINNORM)
-        return SBCE_EINVAL;
+    if (!valid_solve(solve_mode)) return SBCE_EINVAL;
     int rc = check_ptrs(p, pb, true, solve_mode);
     if (rc) return rc;
     if (p->llf && !p->x_d_true) return SBCE_EINVAL;
@@ -360,24 +393,15 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
                                     small2 ? list_cnt : nullptr, s))))
         return rc;
 
-    EstepArgs ea;
-    ea.yd = (const cd*)p->y_d; ea.psid = (const cd*)p->psi_d; ea.theta = (const cd*)p->theta;
-    ea.cons = (const cd*)p->cons; ea.mom = (cd*)(ws + c.mom); ea.done = (early || cv) ? done : nullptr;
-    ea.status = p->status;
-    ea.varn_t = p->varn_t;
+    EstepArgs ea = estep_args(p, ws + c.mom, ws, &c);
+    ea.done = (early || cv) ? done : nullptr;
     if (nz) {                                // the estimate starts at the caller's parameter
         if ((rc = hip_rc(launch_noise_init(pb.B, nz->varn_est, p->varn_t, pb.varn, s)))) return rc;
         ea.varn_t = nz->varn_est;
     }
-    ea.prep = c.has_prep ? (double*)(ws + c.prep) : nullptr;
-    ea.list = c.has_prep ? (int32_t*)(ws + c.list) : nullptr;
-    ea.tree = c.has_prep ? (double*)(ws + c.tree) : nullptr;
     ea.lists_zeroed = small2 && list_cnt != nullptr;
-    MstepArgs ma;
-    ma.yd = ea.yd; ma.yp = (const cd*)p->y_p; ma.psid = ea.psid; ma.up = (const cd*)p->u_p;
-    ma.mom = ea.mom; ma.R = (cd*)(ws + c.R); ma.rhs = (cd*)(ws + c.rhs); ma.theta = (cd*)p->theta;
-    ma.status = p->status; ma.done = ea.done; ma.solve_mode = solve_mode; ma.nbatch = pb.B;
-    set_large(ma, ws, c);
+    MstepArgs ma = mstep_args(pb, p, ea.mom, ws, c, solve_mode);
+    ma.done = ea.done;
 
     EstepArgs eas = ea;                      // superimposed pilots: E-step on y - H x_p
     if (p->x_sup) eas.yd = (const cd*)(ws + c.ysh);
@@ -517,9 +541,7 @@ int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
                    const sbce_noise_opts* o, void* hip_stream) {
     Problem pb;
     if (!make_problem(d, pb) || !p || !o) return SBCE_EINVAL;
-    const void* req[] = {p->y_d, p->y_p, p->psi_d, p->u_p, p->theta, moments};
-    for (const void* q : req)
-        if (!q || !aligned16(q)) return SBCE_EINVAL;
+    if (!required({p->y_d, p->y_p, p->psi_d, p->u_p, p->theta, moments})) return SBCE_EINVAL;
     if (p->varn_t && ((uintptr_t)p->varn_t & 7)) return SBCE_EINVAL;
     if (int rc = check_noise(p, o, pb)) return rc;
     if (pb.B == 0) return SBCE_OK;
@@ -542,22 +564,10 @@ int sbce_estep(const sbce_dims* d, const sbce_ptrs* p, int estep_mode, void* mom
     if (!estep_supported(pb, estep_mode)) return SBCE_EUNSUPPORTED;
     if (pb.B == 0) return SBCE_OK;
     if ((rc = status_init(p->status, pb.B, (hipStream_t)hip_stream))) return rc;
-    EstepArgs ea;
-    ea.yd = (const cd*)p->y_d; ea.psid = (const cd*)p->psi_d; ea.theta = (const cd*)p->theta;
-    ea.cons = (const cd*)p->cons; ea.mom = (cd*)moments; ea.done = nullptr;
-    ea.status = p->status;
-    ea.varn_t = p->varn_t;
-    ea.prep = nullptr;               // workspace optional here: use it when it is large enough
-    ea.list = nullptr;
-    ea.tree = nullptr;
-    if (p->workspace && aligned16(p->workspace)) {
-        const Carve c = carve(pb, SBCE_SOLVE_CHOL);      // the E-step regions come first
-        if (c.has_prep && p->workspace_bytes >= c.total) {
-            ea.prep = (double*)((char*)p->workspace + c.prep);
-            ea.list = (int32_t*)((char*)p->workspace + c.list);
-            ea.tree = (double*)((char*)p->workspace + c.tree);
-        }
-    }
+    // workspace optional here: use it when it is large enough (the E-step regions come first)
+    const Carve c = carve(pb, SBCE_SOLVE_CHOL);
+    const bool use_ws = p->workspace && aligned16(p->workspace) && p->workspace_bytes >= c.total;
+    const EstepArgs ea = estep_args(p, moments, (char*)p->workspace, use_ws ? &c : nullptr);
     return hip_rc(launch_estep(pb, ea, estep_mode, (hipStream_t)hip_stream));
 }
 
@@ -567,9 +577,7 @@ int sbce_mstep(const sbce_dims* d, const sbce_ptrs* p, const void* moments, int 
     Problem pb;
     if (!make_problem(d, pb)) return SBCE_EINVAL;
     if (!chol_supported(pb)) return SBCE_EUNSUPPORTED;
-    if (solve_mode != SBCE_SOLVE_CHOL && solve_mode != SBCE_SOLVE_CHOL_DROP &&
-        solve_mode != SBCE_SOLVE_MINNORM)
-        return SBCE_EINVAL;
+    if (!valid_solve(solve_mode)) return SBCE_EINVAL;
     int rc = check_ptrs(p, pb, true, solve_mode);
     if (rc) return rc;
     if (!moments) return SBCE_EINVAL;
@@ -578,12 +586,7 @@ int sbce_mstep(const sbce_dims* d, const sbce_ptrs* p, const void* moments, int 
     const Carve c = carve(pb, solve_mode);
     char* ws = (char*)p->workspace;
     if ((rc = status_init(p->status, pb.B, s))) return rc;
-    MstepArgs ma;
-    ma.yd = (const cd*)p->y_d; ma.yp = (const cd*)p->y_p; ma.psid = (const cd*)p->psi_d;
-    ma.up = (const cd*)p->u_p; ma.mom = (const cd*)moments; ma.R = (cd*)(ws + c.R);
-    ma.rhs = (cd*)(ws + c.rhs); ma.theta = (cd*)p->theta; ma.status = p->status; ma.done = nullptr;
-    ma.solve_mode = solve_mode; ma.nbatch = pb.B;
-    set_large(ma, ws, c);
+    const MstepArgs ma = mstep_args(pb, p, moments, ws, c, solve_mode);
     const bool small = mstep_small_supported(pb, solve_mode);
     if (small) {
         if ((rc = hip_rc(launch_mstep_small(pb, ma, r_out || rhs_out, s)))) return rc;
@@ -656,12 +659,8 @@ int sbce_debug_mstep_phase(const sbce_dims* d, const sbce_ptrs* p, const void* m
     hipStream_t s = (hipStream_t)hip_stream;
     const Carve c = carve(pb, SBCE_SOLVE_CHOL);
     char* ws = (char*)p->workspace;
-    MstepArgs ma;
-    ma.yd = (const cd*)p->y_d; ma.yp = (const cd*)p->y_p; ma.psid = (const cd*)p->psi_d;
-    ma.up = (const cd*)p->u_p; ma.mom = (const cd*)moments; ma.R = (cd*)(ws + c.R);
-    ma.rhs = (cd*)(ws + c.rhs); ma.theta = (cd*)p->theta; ma.status = nullptr; ma.done = nullptr;
-    ma.solve_mode = SBCE_SOLVE_CHOL; ma.nbatch = pb.B;
-    set_large(ma, ws, c);
+    MstepArgs ma = mstep_args(pb, p, moments, ws, c, SBCE_SOLVE_CHOL);
+    ma.status = nullptr;
     if (phase == 0) return rbuild_herm_supported(pb) ? hip_rc(launch_pilot_factor(pb, ma, s)) : SBCE_OK;
     if (phase == 1 && rbuild_herm_supported(pb)) return hip_rc(launch_rbuild_herm(pb, ma, s));
     return hip_rc(launch_mstep_build(pb, ma, s, rbuild_herm_supported(pb)));
@@ -774,9 +773,7 @@ int sbce_approx_em(const sbce_approx_dims* d, const sbce_approx_ptrs* p, int ite
     if (d->batch < 1 || d->n_ris < 1 || d->n_rx < 1 || d->t_p < 1 || d->t_d < 1 || iters < 1 ||
         !(d->varn > 0.0))
         return SBCE_EINVAL;
-    const void* req[] = {p->y_d, p->y_p, p->psi_d, p->psi_p, p->x_p, p->g};
-    for (const void* q : req)
-        if (!q || !aligned16(q)) return SBCE_EINVAL;
+    if (!required({p->y_d, p->y_p, p->psi_d, p->psi_p, p->x_p, p->g})) return SBCE_EINVAL;
     if (p->varn_t && ((uintptr_t)p->varn_t & 7)) return SBCE_EINVAL;
     if (!approx_supported(d->n_ris, d->n_rx)) return SBCE_EUNSUPPORTED;
     clear_stale_error();
@@ -801,12 +798,8 @@ int sbce_detect(const sbce_detect_dims* d, const sbce_detect_ptrs* p, void* hip_
     if (d->batch < 1 || d->n_tx < 1 || d->n_rx < 1 || d->n_psi < 1 || d->t_d < 1 ||
         !(d->sigma2 > 0.0) || (d->flags & ~SBCE_DETECT_MAXLOG))
         return SBCE_EINVAL;
-    int lgm = 0;
-    while ((1 << lgm) < d->m) ++lgm;
-    if (d->m < 2 || d->m > 64 || (1 << lgm) != d->m) return SBCE_EINVAL;
-    const void* req[] = {p->y_d, p->psi_d, p->cons, p->theta};
-    for (const void* q : req)
-        if (!q || !aligned16(q)) return SBCE_EINVAL;
+    if (d->m < 2 || d->m > 64 || (d->m & (d->m - 1))) return SBCE_EINVAL;   // a power of two
+    if (!required({p->y_d, p->psi_d, p->cons, p->theta})) return SBCE_EINVAL;
     if ((p->llr || p->err) && !p->labels) return SBCE_EINVAL;
     if (p->err && !p->x_d_true) return SBCE_EINVAL;
     if (!aligned16(p->x_d_true) || !aligned16(p->x_hat)) return SBCE_EINVAL;
@@ -820,13 +813,13 @@ int sbce_detect(const sbce_detect_dims* d, const sbce_detect_ptrs* p, void* hip_
     if (need && (!p->workspace || !aligned16(p->workspace))) return SBCE_EINVAL;
     if (p->workspace_bytes < need) return SBCE_EWORKSPACE;
     clear_stale_error();
-    DetectArgs a;
+    DetectArgs a{};                      // lgM, TC and chunks are launch_detect's
     a.yd = (const cd*)p->y_d; a.psid = (const cd*)p->psi_d; a.cons = (const cd*)p->cons;
     a.theta = (const cd*)p->theta; a.labels = p->labels; a.sigma2_t = p->sigma2_t;
     a.xd = (const cd*)p->x_d_true; a.xhat = (cd*)p->x_hat; a.idx = p->idx_hat; a.post = p->post;
     a.llr = p->llr; a.err = p->err;
     a.B = d->batch; a.NT = d->n_tx; a.NR = d->n_rx; a.P = d->n_psi; a.Td = d->t_d; a.M = d->m;
-    a.lgM = lgm; a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0; a.TC = 0; a.chunks = 0;
+    a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0;
     a.sigma2 = d->sigma2;
     return hip_rc(launch_detect(a, (hipStream_t)hip_stream));
 }

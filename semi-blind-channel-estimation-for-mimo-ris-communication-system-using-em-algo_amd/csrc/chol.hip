@@ -41,8 +41,6 @@ namespace {
 constexpr int NB = 16;   // panel width (columns)
 constexpr int KC = 32;   // k-chunk of the left-looking update
 
-typedef double d4v __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------- shared pieces
 // Factor the (updated) w x w diagonal block held in wave-0 registers (lane r < w
 // holds row r in dr[0..15]); writes D (lower, LDS), Di = D^{-1} (lower, LDS),
@@ -604,7 +602,7 @@ void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
             arow[u] = R + (size_t)r * ld + lk;
         }
         // ---- C tiles <- A[rows, jb:jb+16] (C layout) ----
-        d4v cre[MAXT], cim[MAXT];
+        mf4 cre[MAXT], cim[MAXT];
 #pragma unroll
         for (int u = 0; u < MAXT; ++u) {
             const int tau = wave + u * nw;
@@ -697,7 +695,7 @@ void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) X[(lk + 4 * q) * NB + li] = cmk(cre[u][q], cim[u][q]);
             wave_sync();
-            d4v xre = {0.0, 0.0, 0.0, 0.0}, xim = {0.0, 0.0, 0.0, 0.0};
+            mf4 xre = {0.0, 0.0, 0.0, 0.0}, xim = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int s2 = 0; s2 < NB / 4; ++s2) {
                 const cd d = Di[li * NB + 4 * s2 + lk];    // A[j][k] = conj(Di[j][4s+k])
@@ -783,12 +781,12 @@ __device__ __forceinline__ void panel_update_body(const MstepArgs& a, int L, int
     const cd* arow = R + (size_t)r * L + lk;
     // tile 0's right half lies in the strict upper triangle: neither loaded nor stored
     const int nv = tau == 0 ? 1 : 2;
-    d4v cre[2], cim[2], c2[2];
+    mf4 cre[2], cim[2], c2[2];
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
-        cre[v] = d4v{0.0, 0.0, 0.0, 0.0};
-        cim[v] = d4v{0.0, 0.0, 0.0, 0.0};
-        c2[v] = d4v{0.0, 0.0, 0.0, 0.0};
+        cre[v] = mf4{0.0, 0.0, 0.0, 0.0};
+        cim[v] = mf4{0.0, 0.0, 0.0, 0.0};
+        c2[v] = mf4{0.0, 0.0, 0.0, 0.0};
         if (active && v < nv) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -934,7 +932,7 @@ template <bool G3 = false>
 __device__ __forceinline__ void trsm_tile16(cd* R, cd* y, const cd* Di, const cd* cop, const cd* yb,
                                             int L, int NR, int row0, int c0, int w, int li,
                                             int lk, cd* xv, double* yd, cd* ylds = nullptr) {
-    d4v xre = {0.0, 0.0, 0.0, 0.0}, xim = {0.0, 0.0, 0.0, 0.0}, x2 = {0.0, 0.0, 0.0, 0.0};
+    mf4 xre = {0.0, 0.0, 0.0, 0.0}, xim = {0.0, 0.0, 0.0, 0.0}, x2 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int s2 = 0; s2 < NB / 4; ++s2) {
         const cd d = Di[li * NB + 4 * s2 + lk];    // A[j][k] = conj(Di[j][4s+k])
@@ -962,7 +960,7 @@ __device__ __forceinline__ void trsm_tile16(cd* R, cd* y, const cd* Di, const cd
     const bool isre = li < NR, on = li < 2 * NR;
     const int r = isre ? li : li - NR;
     // two accumulation chains of four MFMAs (Re X and Im X parts) instead of one of eight
-    d4v u = {0.0, 0.0, 0.0, 0.0}, u2 = {0.0, 0.0, 0.0, 0.0};
+    mf4 u = {0.0, 0.0, 0.0, 0.0}, u2 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int s2 = 0; s2 < NB / 4; ++s2) {
         const cd v = on ? yb[(4 * s2 + lk) * NR + r] : czero();     // Y_blk[4s+lk][r]
@@ -1053,7 +1051,7 @@ constexpr int kFacMaxTile = (kLargeL + NB - 1) / NB;
 // 16 kk + 4 s + lk of row li), Lph = the half's 16 rows of Lp.
 template <bool G3>
 __device__ __forceinline__ void preupdate_half(const cd* Lph, const cd* av, cd* c, int li, int lk) {
-    d4v cre, cim, c2;
+    mf4 cre, cim, c2;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         cre[q] = c[q].x;
@@ -1257,7 +1255,7 @@ __device__ __forceinline__ void panel_factor_body(const MstepArgs& a, int L, int
     if (wave == 0) {
         if (wB > 0) {
             // B's diagonal tile: C_B1 -= X_A1 X_A1^H, then factor
-            d4v cre = {0.0, 0.0, 0.0, 0.0}, cim = {0.0, 0.0, 0.0, 0.0}, c2;
+            mf4 cre = {0.0, 0.0, 0.0, 0.0}, cim = {0.0, 0.0, 0.0, 0.0}, c2;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int c = lk + 4 * q;
@@ -1315,7 +1313,7 @@ __device__ __forceinline__ void panel_factor_body(const MstepArgs& a, int L, int
                 load_ycomp(y, L, NR, row0 + 3 * NB, li, lk, more, ycur);
             }
             if (wB > 0) {
-                d4v cre, cim, c2;
+                mf4 cre, cim, c2;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     cre[q] = cb[q].x;

@@ -5,14 +5,9 @@
 // "Proposed method/QAM.py":164-185 on the MIMO posterior; cons is any table, labels any
 // permutation (no grid structure is used anywhere).
 //
-// Work split.  One workgroup of 4 waves takes TC consecutive symbols of ONE trial (TC = 4 when
-// J >= 4096, else 16; a function of the shape only).  theta of the trial is staged once per
-// workgroup in LDS, in tiles of 32 rows of P, and every wave forms the effective channels
-// H_t[r][a] = sum_p psi_t[p] theta[(p NT + a) NR + r] of its (up to 4) symbols from each tile:
-// lane = (entry, half), the half-sums run over even / odd p in ascending order and are added
-// even + odd.  Then ONE WAVE PER SYMBOL: with Q = M^(NT-1) prefixes q (streams 0..NT-2) and the
-// last stream s, lane l of the wave owns the rows q = 64 qb + l and loops over s; the residual
-// y - sum_{a<NT-1} H[:,a] x_a is formed once per row, each distance costs NR complex FMAs.
+// Work split, effective channels H_t and the distance arithmetic: hyp_enum.h (shared with
+// loglik.hip).  One workgroup of 4 waves takes TC consecutive symbols of ONE trial, then ONE WAVE
+// PER SYMBOL: lane l owns the prefix rows q = 64 qb + l and loops over the last stream s.
 //
 // Log-domain scheme.  The quantities wanted are sums of e^{-d_j/s2} over the classes
 // C(a, v) = {j : x_j[a] = cons[v]} (NT M classes; bit sums are unions of M/2 classes).  A global
@@ -30,22 +25,14 @@
 // Every reduction (DPP wave sums, butterflies, the qb loop) has an order fixed by the shape, no
 // floating-point atomic is used and nothing is shared between workgroups: trial b of a B-trial
 // call gives bitwise the result of a B = 1 call.  The error counters are integer atomic adds.
-#include "sbce_internal.h"
+#include "hyp_enum.h"
 
 namespace sbce {
 
 namespace {
 
-constexpr int kDetThreads = 256;
-constexpr int kDetWaves = 4;
-constexpr int kDetPT = 32;          // rows of P per staged theta tile (even: half = parity of p)
-constexpr int kDetMaxSym = 4;       // symbols per wave of a workgroup (TC <= 16)
-constexpr int kDetMaxNE = 32;       // NT * NR
-constexpr int kDetMaxCls = 128;     // NT * M (M^NT <= 65536)
+constexpr int kMaxCls = 128;        // NT * M (M^NT <= 65536)
 
-__device__ __forceinline__ cd shfl_xor_c(cd v, int m) {
-    return cmk(shfl_xor_d(v.x, m), shfl_xor_d(v.y, m));
-}
 __device__ __forceinline__ unsigned long long dbits(double v) {
     return (unsigned long long)__double_as_longlong(v);
 }
@@ -53,50 +40,14 @@ __device__ __forceinline__ double bitsd(unsigned long long v) {
     return __longlong_as_double((long long)v);
 }
 
-// ||r - h c||^2 over the NRP (padded, zero) rows, in one fixed fma sequence: pass 1 and pass 2
-// get the same bits
 template <int NRP>
-__device__ __forceinline__ double dist2(const cd* r, const cd* h, cd c) {
-    double d = 0.0;
-#pragma unroll
-    for (int i = 0; i < NRP; ++i) {
-        double tx = fma(-h[i].x, c.x, r[i].x);
-        tx = fma(h[i].y, c.y, tx);
-        double ty = fma(-h[i].x, c.y, r[i].y);
-        ty = fma(-h[i].y, c.x, ty);
-        d = fma(tx, tx, d);
-        d = fma(ty, ty, d);
-    }
-    return d;
-}
-
-// the row's residual y - sum_{a < NT-1} H[:,a] cons[digit_a(q)]
-template <int NRP>
-__device__ __forceinline__ void residual(cd* rr, const cd* yv, const cd* Hw, const cd* cons_s,
-                                         int q, int NT, int NR, int lgM, int M) {
-#pragma unroll
-    for (int i = 0; i < NRP; ++i) rr[i] = yv[i];
-    for (int a = 0; a < NT - 1; ++a) {
-        const cd c = cons_s[(q >> (lgM * (NT - 2 - a))) & (M - 1)];
-#pragma unroll
-        for (int i = 0; i < NRP; ++i) {
-            const cd h = csel(i < NR, Hw[a * NR + (i < NR ? i : 0)], czero());
-            rr[i].x = fma(-h.x, c.x, rr[i].x);
-            rr[i].x = fma(h.y, c.y, rr[i].x);
-            rr[i].y = fma(-h.x, c.y, rr[i].y);
-            rr[i].y = fma(-h.y, c.x, rr[i].y);
-        }
-    }
-}
-
-template <int NRP>
-__global__ __launch_bounds__(kDetThreads) void detect_kernel(DetectArgs a) {
-    __shared__ cd th_s[kDetPT * kDetMaxNE];
+__global__ __launch_bounds__(kHypThreads) void detect_kernel(DetectArgs a) {
+    __shared__ cd th_s[kHypPT * kHypMaxNE];
     __shared__ cd cons_s[64];
     __shared__ int lab_s[64];
-    __shared__ cd H_s[kDetWaves][kDetMaxSym][kDetMaxNE];
-    __shared__ unsigned long long cmin_s[kDetWaves][kDetMaxCls];
-    __shared__ double csum_s[kDetWaves][kDetMaxCls];
+    __shared__ cd H_s[kHypWaves][kHypMaxSym][kHypMaxNE];
+    __shared__ unsigned long long cmin_s[kHypWaves][kMaxCls];
+    __shared__ double csum_s[kHypWaves][kMaxCls];
 
     const int NT = a.NT, NR = a.NR, P = a.P, Td = a.Td, M = a.M, lgM = a.lgM;
     const int NE = NT * NR;
@@ -111,36 +62,7 @@ __global__ __launch_bounds__(kDetThreads) void detect_kernel(DetectArgs a) {
         lab_s[tid] = a.labels ? a.labels[tid] : tid;
     }
 
-    // ---- effective channels of this wave's symbols, theta staged tile by tile
-    {
-        const cd* th = a.theta + (size_t)b * P * NE;
-        const int e = lane & 31, half = lane >> 5;
-        cd acc[kDetMaxSym];
-#pragma unroll
-        for (int k = 0; k < kDetMaxSym; ++k) acc[k] = czero();
-        for (int p0 = 0; p0 < P; p0 += kDetPT) {
-            const int np = P - p0 < kDetPT ? P - p0 : kDetPT;
-            __syncthreads();
-            for (int i = tid; i < np * NE; i += kDetThreads) th_s[i] = th[(size_t)p0 * NE + i];
-            __syncthreads();
-            if (e < NE) {
-#pragma unroll
-                for (int k = 0; k < kDetMaxSym; ++k) {
-                    const int t = t0 + w + kDetWaves * k;
-                    if (t < tend) {
-                        const cd* ps = a.psid + (bt + t) * P + p0;
-                        for (int pp = half; pp < np; pp += 2)
-                            acc[k] = cfma(acc[k], ps[pp], th_s[pp * NE + e]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kDetMaxSym; ++k) {
-            const cd o = shfl_xor_c(acc[k], 32);
-            if (half == 0 && e < NE) H_s[w][k][e] = cadd(acc[k], o);   // even + odd
-        }
-    }
+    heff_stage(H_s, th_s, a.theta, a.psid, b, bt, P, NE, t0, tend, tid, lane, w);
     __syncthreads();
 
     const int Q = 1 << (lgM * (NT - 1));
@@ -153,8 +75,8 @@ __global__ __launch_bounds__(kDetThreads) void detect_kernel(DetectArgs a) {
     double* csum = csum_s[w];
     int nse = 0, nbe = 0;
 
-    for (int k = 0; k < kDetMaxSym; ++k) {
-        const int t = t0 + w + kDetWaves * k;
+    for (int k = 0; k < kHypMaxSym; ++k) {
+        const int t = t0 + w + kHypWaves * k;
         if (t >= tend) break;                       // wave-uniform
         const cd* Hw = H_s[w][k];
         cd yv[NRP], hl[NRP];
@@ -290,24 +212,19 @@ __global__ __launch_bounds__(kDetThreads) void detect_kernel(DetectArgs a) {
 
 template <int NRP>
 hipError_t launch_nrp(const DetectArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(detect_kernel<NRP>, dim3((unsigned)(a.B * a.chunks)), dim3(kDetThreads), 0, s, a);
+    hipLaunchKernelGGL(detect_kernel<NRP>, dim3((unsigned)(a.B * a.chunks)), dim3(kHypThreads), 0, s, a);
     return hipGetLastError();
 }
 
 }  // namespace
 
 bool detect_supported(int NT, int NR, int M) {
-    if (NT < 1 || NT > 4 || NR < 1 || NR > 8 || M < 2 || M > 64) return false;
-    long long J = 1;
-    for (int i = 0; i < NT; ++i) J *= M;
-    return J <= kDetectMaxJ && NT * M <= kDetMaxCls;
+    return hyp_supported(NT, NR, M) && NT * M <= kMaxCls;
 }
 
 hipError_t launch_detect(DetectArgs a, hipStream_t s) {
-    long long J = 1;
-    for (int i = 0; i < a.NT; ++i) J *= a.M;
-    a.TC = J >= 4096 ? kDetWaves : kDetWaves * kDetMaxSym;
-    a.chunks = (a.Td + a.TC - 1) / a.TC;
+    a.lgM = hyp_log2(a.M);
+    hyp_split(a.NT, a.M, a.Td, a.TC, a.chunks);
     if ((long long)a.B * a.chunks > 0x7fffffffLL) return hipErrorInvalidValue;
     if (a.err) {
         hipError_t e = hipMemsetAsync(a.err, 0, (size_t)a.B * 2 * sizeof(int32_t), s);

@@ -405,7 +405,6 @@ __global__ __launch_bounds__(256) void estep_kernel(EstepArgs a, EstepConst c) {
 // U_{s0} + V_{s1} (U_s = -2(y - h_0 x_s), V_s = 2 h_1 x_s, layout [kk][s]:
 // conflict-free ds_read_b64), and alpha_i = ||p_i||^2 is tabulated 256 at a time.
 // ============================================================================
-typedef double d4v __attribute__((ext_vector_type(4)));
 
 // Initial bound for the hypothesis sweep: the distance ||y - H x_c||^2 of x_c = the
 // per-stream nearest constellation points of the regularised LS estimate
@@ -1039,7 +1038,7 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                     nrm = fma(v, v, nrm);
                 }
                 if (lane < 32) s_tab[lane] = nrm;
-                d4v cx = {0.0, 0.0, 0.0, 0.0};
+                mf4 cx = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int s = 0; s < STEPS; ++s)
                     cx = __builtin_amdgcn_mfma_f64_16x16x4f64(s_U[(4 * s + rq) * 16 + col], vreg[s],
@@ -1107,13 +1106,13 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                     if (!pass) continue;
                 }
                 ++groups;
-                d4v acc[TU];
+                mf4 acc[TU];
 #pragma unroll
                 for (int u = 0; u < TU; ++u) {
                     if (V16) {            // rows rq + 4j of tile tg + u: 4 consecutive doubles
                         const cd lo = *reinterpret_cast<const cd*>(s_al + (tg + u) * 16 + rq * 4);
                         const cd hi = *reinterpret_cast<const cd*>(s_al + (tg + u) * 16 + rq * 4 + 2);
-                        acc[u] = d4v{lo.x, lo.y, hi.x, hi.y};
+                        acc[u] = mf4{lo.x, lo.y, hi.x, hi.y};
                     } else {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) acc[u][j] = s_al[(tg + u) * 16 + rq + 4 * j];

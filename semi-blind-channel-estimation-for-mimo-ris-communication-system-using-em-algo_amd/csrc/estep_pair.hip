@@ -33,7 +33,6 @@ __device__ unsigned long long g_estep_pair;
 namespace {
 
 constexpr int kPairWaves = 4;
-typedef double d4v __attribute__((ext_vector_type(4)));
 
 struct PairConst {
     int B, Td, stride;     // prep record doubles per symbol
@@ -224,9 +223,9 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
             double ap[4];
 #pragma unroll
             for (int s = 0; s < 4; ++s) ap[s] = ar[s] * E12[(4 * s + g) * 16 + x2];
-            d4v V[4];
+            mf4 V[4];
 #pragma unroll
-            for (int w = 0; w < 4; ++w) V[w] = d4v{0.0, 0.0, 0.0, 0.0};
+            for (int w = 0; w < 4; ++w) V[w] = mf4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll

@@ -1,15 +1,15 @@
 // Observed-data log-likelihood (sbce_loglik) and the truth-free convergence stop of the EM chain
 // (sbce_em_conv), DESIGN.md §3.10.  Per trial b with s2 = varn_b^2 and J = M^NT hypotheses x_j
-// (itertools.product order, first stream slowest), d_j = ||y_t - H_t x_j||^2 with detect.hip's
+// (itertools.product order, first stream slowest), d_j = ||y_t - H_t x_j||^2 with the effective
 // channel H_t[r][a] = sum_p psi_t[p] theta[(p NT + a) NR + r]:
 //   ll_sym[b][t] = -d_min/s2 + log sum_j e^{-(d_j - d_min)/s2} - log J - NR log(pi s2)
 //   ll[b]        = sum_t ll_sym[b][t] + sum_pilots ( -||y_p - H_c u_p||^2/s2 - NR log(pi s2) )
 //
 // loglik_sym_kernel   grid B chunks + B npb workgroups of 4 waves.
-//   Symbol workgroups (the first B chunks) use detect.hip's work split: TC consecutive symbols of
-//   ONE trial (TC = 4 when J >= 4096, else 16), theta staged through LDS in tiles of 32 rows of P,
-//   every wave forms the effective channels of its (up to 4) symbols, then ONE WAVE PER SYMBOL:
-//   lane l owns the prefix rows q = 64 qb + l (streams 0..NT-2) and loops over the last stream.
+//   Symbol workgroups (the first B chunks) use the work split, the effective channels and the
+//   distance arithmetic of hyp_enum.h (shared with detect.hip): TC consecutive symbols of ONE
+//   trial, then ONE WAVE PER SYMBOL: lane l owns the prefix rows q = 64 qb + l (streams 0..NT-2)
+//   and loops over the last stream.
 //   Only one scalar per symbol is wanted, so a lane keeps ONE online log-sum-exp pair (rm, rS)
 //   over all its hypotheses (rS = sum e^{-(d - rm)/s2}, rescaled when rm drops) and the wave
 //   combines the 64 pairs once: m = wave min of rm, S = DPP wave sum of rS e^{-(rm - m)/s2}.
@@ -18,8 +18,9 @@
 //   A term with (d - rm)/s2 >= 50 for EVERY lane of the wave is skipped (rm >= d_min, so the
 //   dropped term is below e^-50 of the sum: over J <= 65536 terms less than 2e-17 relative).
 //   Pilot workgroups (the last B npb): item i = 256 k + tid is (pilot t, antenna r), r fastest,
-//   as noise.hip's pilot items; theta walks the same LDS tiles, u_p is read from global memory.
-//   The block sum of ||y_p - H_c u_p||^2 (DPP wave sums, then the four waves in order) goes to
+//   as noise.hip's pilot items (the same p-then-a fma order, there on tiles of 8 phases); theta
+//   walks the same LDS tiles, u_p is read from global memory.  The block sum of
+//   ||y_p - H_c u_p||^2 (DPP wave sums, then the four waves in order: block_sum4) goes to
 //   ppart[b][k].
 // loglik_final_kernel one wave per trial: lane l adds ll_sym[b][l], [l + 64], ... in ascending
 //   order, one DPP wave sum, then lane 0 adds the pilot block sums in index order.
@@ -30,64 +31,20 @@
 //   log-likelihood): ||theta - theta_prev||^2 and ||theta||^2 (thread-strided partial sums in
 //   ascending order, DPP wave sums, the four waves in order), the histories, theta_prev = theta
 //   and the stop decision in product form (no division; a NaN compares false and never stops).
-#include "sbce_internal.h"
+#include "hyp_enum.h"
 
 namespace sbce {
 
 namespace {
 
-constexpr int kLlThreads = 256;
-constexpr int kLlWaves = 4;
-constexpr int kLlPT = 32;           // rows of P per staged theta tile (even: half = parity of p)
-constexpr int kLlMaxSym = 4;        // symbols per wave of a workgroup (TC <= 16)
-constexpr int kLlMaxNE = 32;        // NT * NR
-constexpr double kLlSkip = 50.0;    // (d - rm)/s2 at which a term is dropped
-
-__device__ __forceinline__ cd ll_shfl_xor_c(cd v, int m) {
-    return cmk(shfl_xor_d(v.x, m), shfl_xor_d(v.y, m));
-}
-
-// ||r - h c||^2 over the NRP (padded, zero) rows, detect.hip's fma sequence
-template <int NRP>
-__device__ __forceinline__ double ll_dist2(const cd* r, const cd* h, cd c) {
-    double d = 0.0;
-#pragma unroll
-    for (int i = 0; i < NRP; ++i) {
-        double tx = fma(-h[i].x, c.x, r[i].x);
-        tx = fma(h[i].y, c.y, tx);
-        double ty = fma(-h[i].x, c.y, r[i].y);
-        ty = fma(-h[i].y, c.x, ty);
-        d = fma(tx, tx, d);
-        d = fma(ty, ty, d);
-    }
-    return d;
-}
-
-// the row's residual y - sum_{a < NT-1} H[:,a] cons[digit_a(q)]
-template <int NRP>
-__device__ __forceinline__ void ll_residual(cd* rr, const cd* yv, const cd* Hw, const cd* cons_s,
-                                            int q, int NT, int NR, int lgM, int M) {
-#pragma unroll
-    for (int i = 0; i < NRP; ++i) rr[i] = yv[i];
-    for (int a = 0; a < NT - 1; ++a) {
-        const cd c = cons_s[(q >> (lgM * (NT - 2 - a))) & (M - 1)];
-#pragma unroll
-        for (int i = 0; i < NRP; ++i) {
-            const cd h = csel(i < NR, Hw[a * NR + (i < NR ? i : 0)], czero());
-            rr[i].x = fma(-h.x, c.x, rr[i].x);
-            rr[i].x = fma(h.y, c.y, rr[i].x);
-            rr[i].y = fma(-h.x, c.y, rr[i].y);
-            rr[i].y = fma(-h.y, c.x, rr[i].y);
-        }
-    }
-}
+constexpr double kSkip = 50.0;      // (d - rm)/s2 at which a term is dropped
 
 template <int NRP>
-__global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
-    __shared__ cd th_s[kLlPT * kLlMaxNE];
+__global__ __launch_bounds__(kHypThreads) void loglik_sym_kernel(LoglikArgs a) {
+    __shared__ cd th_s[kHypPT * kHypMaxNE];
     __shared__ cd cons_s[64];
-    __shared__ cd H_s[kLlWaves][kLlMaxSym][kLlMaxNE];
-    __shared__ double red[kLlWaves];
+    __shared__ cd H_s[kHypWaves][kHypMaxSym][kHypMaxNE];
+    __shared__ double red[kHypWaves];
 
     const int NT = a.NT, NR = a.NR, P = a.P, Td = a.Td, M = a.M, lgM = a.lgM;
     const int NE = NT * NR;
@@ -100,16 +57,16 @@ __global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
         const int b = pi / a.npb, k = pi - b * a.npb;
         if (a.done && a.done[b]) return;                 // block-uniform: the trial has stopped
         const int Tp = a.Tp;
-        const int i = k * kLlThreads + tid;
+        const int i = k * kHypThreads + tid;
         const bool act = i < Tp * NR;
         const int t = act ? i / NR : 0, r = act ? i - t * NR : 0;
         const cd* th = a.theta + (size_t)b * P * NE;
         const cd* upg = a.up + ((size_t)b * Tp + t) * ((size_t)P * NT);
         cd h = czero();                                  // (H_c u_p)_r
-        for (int p0 = 0; p0 < P; p0 += kLlPT) {
-            const int np = P - p0 < kLlPT ? P - p0 : kLlPT;
+        for (int p0 = 0; p0 < P; p0 += kHypPT) {
+            const int np = P - p0 < kHypPT ? P - p0 : kHypPT;
             __syncthreads();
-            for (int e = tid; e < np * NE; e += kLlThreads) th_s[e] = th[(size_t)p0 * NE + e];
+            for (int e = tid; e < np * NE; e += kHypThreads) th_s[e] = th[(size_t)p0 * NE + e];
             __syncthreads();
             if (act)
                 for (int pp = 0; pp < np; ++pp)
@@ -117,10 +74,8 @@ __global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
                         h = cfma(h, th_s[(pp * NT + ai) * NR + r], upg[(p0 + pp) * NT + ai]);
         }
         double q = act ? cabs2(csub(a.yp[((size_t)b * Tp + t) * NR + r], h)) : 0.0;
-        q = wave_sum_dpp(q);
-        if (lane == 0) red[w] = q;
-        __syncthreads();
-        if (tid == 0) a.ppart[(size_t)b * a.npb + k] = ((red[0] + red[1]) + red[2]) + red[3];
+        q = block_sum4(wave_sum_dpp(q), red, lane, w);
+        if (tid == 0) a.ppart[(size_t)b * a.npb + k] = q;
         return;
     }
 
@@ -132,36 +87,7 @@ __global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
 
     if (tid < M) cons_s[tid] = a.cons[tid];
 
-    // ---- effective channels of this wave's symbols, theta staged tile by tile (detect.hip)
-    {
-        const cd* th = a.theta + (size_t)b * P * NE;
-        const int e = lane & 31, half = lane >> 5;
-        cd acc[kLlMaxSym];
-#pragma unroll
-        for (int k = 0; k < kLlMaxSym; ++k) acc[k] = czero();
-        for (int p0 = 0; p0 < P; p0 += kLlPT) {
-            const int np = P - p0 < kLlPT ? P - p0 : kLlPT;
-            __syncthreads();
-            for (int i = tid; i < np * NE; i += kLlThreads) th_s[i] = th[(size_t)p0 * NE + i];
-            __syncthreads();
-            if (e < NE) {
-#pragma unroll
-                for (int k = 0; k < kLlMaxSym; ++k) {
-                    const int t = t0 + w + kLlWaves * k;
-                    if (t < tend) {
-                        const cd* ps = a.psid + (bt + t) * P + p0;
-                        for (int pp = half; pp < np; pp += 2)
-                            acc[k] = cfma(acc[k], ps[pp], th_s[pp * NE + e]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kLlMaxSym; ++k) {
-            const cd o = ll_shfl_xor_c(acc[k], 32);
-            if (half == 0 && e < NE) H_s[w][k][e] = cadd(acc[k], o);   // even + odd
-        }
-    }
+    heff_stage(H_s, th_s, a.theta, a.psid, b, bt, P, NE, t0, tend, tid, lane, w);
     __syncthreads();
 
     const int Q = 1 << (lgM * (NT - 1));
@@ -169,14 +95,14 @@ __global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
     const double v = a.varn_t ? a.varn_t[b] : a.varn;
     const double s2 = v * v;
     const double inv = 1.0 / s2;
-    const double thr = kLlSkip * s2;
+    const double thr = kSkip * s2;
     const double cst = log((double)Q * (double)M) + (double)NR * log(M_PI * s2);
     // Q is a power of two: below 64 there is one row block and the lanes past Q own nothing,
     // from 64 on every lane owns a row of every block
     const bool valid = lane < Q;
 
-    for (int k = 0; k < kLlMaxSym; ++k) {
-        const int t = t0 + w + kLlWaves * k;
+    for (int k = 0; k < kHypMaxSym; ++k) {
+        const int t = t0 + w + kHypWaves * k;
         if (t >= tend) break;                            // wave-uniform
         const cd* Hw = H_s[w][k];
         cd yv[NRP], hl[NRP];
@@ -190,9 +116,9 @@ __global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
         for (int qb = 0; qb < nqb; ++qb) {
             const int q = (qb << 6) + lane;
             cd rr[NRP];
-            ll_residual<NRP>(rr, yv, Hw, cons_s, q, NT, NR, lgM, M);
+            residual<NRP>(rr, yv, Hw, cons_s, q, NT, NR, lgM, M);
             for (int s = 0; s < M; ++s) {
-                const double d = ll_dist2<NRP>(rr, hl, cons_s[s]);
+                const double d = dist2<NRP>(rr, hl, cons_s[s]);
                 if (!__any(d - rm < thr)) continue;      // below e^-50 of every lane's sum
                 const bool lt = d < rm;
                 const double e = fexp_neg(-fabs(d - rm) * inv);
@@ -210,8 +136,8 @@ __global__ __launch_bounds__(kLlThreads) void loglik_sym_kernel(LoglikArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kLlThreads) void loglik_final_kernel(LoglikArgs a) {
-    const int b = blockIdx.x * kLlWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kHypThreads) void loglik_final_kernel(LoglikArgs a) {
+    const int b = blockIdx.x * kHypWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= a.B) return;                                // wave-uniform
     if (a.done && a.done[b]) return;
     double acc = 0.0;
@@ -229,7 +155,7 @@ __global__ __launch_bounds__(kLlThreads) void loglik_final_kernel(LoglikArgs a) 
 template <int NRP>
 hipError_t launch_sym(const LoglikArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(loglik_sym_kernel<NRP>, dim3((unsigned)(a.B * (a.chunks + a.npb))),
-                       dim3(kLlThreads), 0, s, a);
+                       dim3(kHypThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -288,22 +214,18 @@ __global__ __launch_bounds__(256) void conv_step_kernel(ConvArgs c) {
 
 bool loglik_supported(const Problem& pb) {
     if (pb.M > 64 || (pb.M & (pb.M - 1))) return false;  // the table is indexed by bit fields
-    return detect_supported(pb.NT, pb.NR, pb.M);
+    return hyp_supported(pb.NT, pb.NR, pb.M);
 }
 
 int loglik_npb(const Problem& pb) {
-    return (int)(((long)pb.Tp * pb.NR + kLlThreads - 1) / kLlThreads);
+    return (int)(((long)pb.Tp * pb.NR + kHypThreads - 1) / kHypThreads);
 }
 
 hipError_t launch_loglik(const Problem& pb, LoglikArgs a, hipStream_t s) {
     a.B = pb.B; a.NT = pb.NT; a.NR = pb.NR; a.P = pb.P; a.Tp = pb.Tp; a.Td = pb.Td; a.M = pb.M;
     a.varn = pb.varn;
-    a.lgM = 0;
-    while ((1 << a.lgM) < pb.M) ++a.lgM;
-    long long J = 1;
-    for (int i = 0; i < pb.NT; ++i) J *= pb.M;
-    a.TC = J >= 4096 ? kLlWaves : kLlWaves * kLlMaxSym;
-    a.chunks = (pb.Td + a.TC - 1) / a.TC;
+    a.lgM = hyp_log2(pb.M);
+    hyp_split(pb.NT, pb.M, pb.Td, a.TC, a.chunks);
     a.npb = loglik_npb(pb);
     if ((long long)pb.B * (a.chunks + a.npb) > 0x7fffffffLL) return hipErrorInvalidValue;
     hipError_t e;
@@ -312,8 +234,8 @@ hipError_t launch_loglik(const Problem& pb, LoglikArgs a, hipStream_t s) {
     else if (pb.NR <= 4) e = launch_sym<4>(a, s);
     else e = launch_sym<8>(a, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(loglik_final_kernel, dim3((pb.B + kLlWaves - 1) / kLlWaves), dim3(kLlThreads),
-                       0, s, a);
+    hipLaunchKernelGGL(loglik_final_kernel, dim3((pb.B + kHypWaves - 1) / kHypWaves),
+                       dim3(kHypThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -37,16 +37,11 @@ namespace sbce {
 
 namespace {
 
-typedef double d4v __attribute__((ext_vector_type(4)));
 constexpr int TB = 64;            // tile of the blocked factorisation (mstep_large.hip)
 constexpr int KS = 16;            // k-chunk of the Gram tiles
 constexpr int kLanczosSteps = 4;   // lambda_max to ~10 % (the cut carries a 32x margin)
 constexpr double kCutSafety = 32.0;   // tau = kCutSafety * cut (see the header comment)
 constexpr double kEps = 2.220446049250313e-16;   // numpy.finfo(float).eps
-
-__device__ __forceinline__ d4v mfma4(double a, double b, d4v c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // deterministic block reductions (256 threads, fixed tree order)
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -279,13 +274,13 @@ __global__ __launch_bounds__(256) void gram_kernel(MstepArgs a, int L, int ntile
     const int li = lane & 15, lk = lane >> 4;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
     const int nb = (L + TB - 1) / TB;
-    d4v cre[2][2], cim[2][2], c2[2][2];
+    mf4 cre[2][2], cim[2][2], c2[2][2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
-            cre[u][v] = d4v{0.0, 0.0, 0.0, 0.0};
-            cim[u][v] = d4v{0.0, 0.0, 0.0, 0.0};
+            cre[u][v] = mf4{0.0, 0.0, 0.0, 0.0};
+            cim[u][v] = mf4{0.0, 0.0, 0.0, 0.0};
             csub_init<G3>(cre[u][v], cim[u][v], c2[u][v]);
         }
     for (int K = ti; K < nb; ++K) {

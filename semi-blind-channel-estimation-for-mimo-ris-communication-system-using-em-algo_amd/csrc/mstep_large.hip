@@ -31,14 +31,9 @@ namespace sbce {
 
 namespace {
 
-typedef double d4v __attribute__((ext_vector_type(4)));
 constexpr int TB = 64;      // tile of the blocked factorisation and of the R build
 constexpr int KS = 16;      // k-chunk staged in LDS by the tile GEMM
 constexpr int kTileGroup = 4;   // column blocks per trailing update (tile_herk_kernel K <= 256)
-
-__device__ __forceinline__ d4v mfma4(double a, double b, d4v c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // ---------------------------------------------------------------- pilot factorisation
 // One wave per (pilot symbol, trial).  l* = argmax |u_l|; x'[a] = u[p* NT + a],
@@ -217,13 +212,13 @@ __global__ __launch_bounds__(256) void rbuild_herm_kernel(MstepArgs a, int B, in
         soff[r] = dg ? (comp ? j : i) * (NT + 1) : i * NT + j;
         sdiagim[r] = !dg && comp;                 // imaginary part of an off-diagonal
     }
-    d4v cr[TPW][NCT], ci[TPW][NCT];
+    mf4 cr[TPW][NCT], ci[TPW][NCT];
 #pragma unroll
     for (int u = 0; u < TPW; ++u)
 #pragma unroll
         for (int v = 0; v < NCT; ++v) {
-            cr[u][v] = d4v{0.0, 0.0, 0.0, 0.0};
-            ci[u][v] = d4v{0.0, 0.0, 0.0, 0.0};
+            cr[u][v] = mf4{0.0, 0.0, 0.0, 0.0};
+            ci[u][v] = mf4{0.0, 0.0, 0.0, 0.0};
         }
     const cd* psd = a.psid + (size_t)b * Td * P;
     const cd* mom = a.mom + (size_t)b * Td * MS;
@@ -441,13 +436,13 @@ __global__ __launch_bounds__(256) void tile_gemm_kernel(MstepArgs a, int L, int 
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
     const int kmax = (L - k0) < TB ? (L - k0) : TB;
 
-    d4v cre[2][2], cim[2][2], c2[2][2];
+    mf4 cre[2][2], cim[2][2], c2[2][2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
-            cre[u][v] = d4v{0.0, 0.0, 0.0, 0.0};
-            cim[u][v] = d4v{0.0, 0.0, 0.0, 0.0};
+            cre[u][v] = mf4{0.0, 0.0, 0.0, 0.0};
+            cim[u][v] = mf4{0.0, 0.0, 0.0, 0.0};
             if (HERK) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -576,7 +571,7 @@ __global__ __launch_bounds__(256) void tile_herk_kernel(MstepArgs a, int L, int 
     const int li = lane & 15, lk = lane >> 4;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
 
-    d4v cre[2][2], cim[2][2], c2[2][2];
+    mf4 cre[2][2], cim[2][2], c2[2][2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll

@@ -38,9 +38,7 @@ constexpr int kStageMf = 1024;                // the MFMA build's symbol chunks
 // (the symbols staged in LDS by chunks, all loads of a chunk in flight at once).  B^H rides along
 // as an (L x T) x (T x n_rx) product on row tiles of 16.  The NT(NT+1)/2 blocks and NT row tiles
 // are spread over the 4 waves.  Results to LDS (R: [L][LD], B^H: [L][NR]) over the staging area.
-typedef double d4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void cmfma(d4v& cre, d4v& cim, cd x, cd y) {   // C += x * y
+__device__ __forceinline__ void cmfma(mf4& cre, mf4& cim, cd x, cd y) {   // C += x * y
     cre = __builtin_amdgcn_mfma_f64_16x16x4f64(x.x, y.x, cre, 0, 0, 0);
     cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-x.y, y.y, cre, 0, 0, 0);
     cim = __builtin_amdgcn_mfma_f64_16x16x4f64(x.x, y.y, cim, 0, 0, 0);
@@ -62,7 +60,7 @@ __device__ __forceinline__ void mfma_build(const MstepArgs& a, int b, int P, int
     constexpr int MS = NT + NT * NT;
     const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
     int bi[IPW], bj[IPW], tq[IPW];                    // item: block (bi, bj) or B^H row tile tq
-    d4v cre[IPW], cim[IPW];
+    mf4 cre[IPW], cim[IPW];
 #pragma unroll
     for (int s = 0; s < IPW; ++s) {
         const int it = wave + 4 * s;
@@ -75,7 +73,7 @@ __device__ __forceinline__ void mfma_build(const MstepArgs& a, int b, int P, int
         } else {
             tq[s] = it - NBLK;                       // >= LT: no item
         }
-        cre[s] = d4v{0.0, 0.0, 0.0, 0.0};
+        cre[s] = mf4{0.0, 0.0, 0.0, 0.0};
         cim[s] = cre[s];
     }
     // pilots, TPC symbols (a multiple of 4) per LDS chunk: u_p [TPC][L], y_p [TPC][NR]
@@ -512,7 +510,7 @@ mstep_small2_build_kernel(MstepArgs a, int P, int Tp, int Td, int L) {
     const bool con = li < NT * NR;
     const int VP = bh ? NT * Tp : Tp;                // virtual symbols: pilot slots, then data
     const int V = VP + Td;
-    d4v p1 = {0.0, 0.0, 0.0, 0.0}, p2 = p1, p3 = p1;
+    mf4 p1 = {0.0, 0.0, 0.0, 0.0}, p2 = p1, p3 = p1;
     auto mfma3 = [&](cd x, cd y) {
         p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x.x, y.x, p1, 0, 0, 0);
         p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(x.y, y.y, p2, 0, 0, 0);
@@ -837,7 +835,7 @@ __global__ __launch_bounds__(64) void mstep_small3_solve_kernel(MstepArgs a, int
     const cd* rh = a.rhs + (size_t)b * L * NR;
     const int li = lane & 15, lk = lane >> 4;
     // ---- trailing matrix: tiles (0,0), (1,0), (1,1) as [re, im] accumulators --------------------
-    d4v cre[3], cim[3];
+    mf4 cre[3], cim[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
         const int ti = t == 0 ? 0 : 1, tj = t == 2 ? 1 : 0;

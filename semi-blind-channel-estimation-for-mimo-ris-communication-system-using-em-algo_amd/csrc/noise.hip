@@ -3,7 +3,7 @@
 // (m_t, S_t) the E-step of the same iteration left in the workspace,
 //   Q       = sum_pilots ||y_p - H_c u_p||^2 + sum_data ( ||y_t - H_t m_t||^2 + tr(H_t C_t H_t^H) ),
 //   sigma^2 = Q / (n_rx (T_p + T_d)),   C_t = S_t - m_t m_t^H,
-//   H_t[r][a] = sum_p psi_t[p] theta[(p n_tx + a) n_rx + r]      (detect.hip's channel),
+//   H_t[r][a] = sum_p psi_t[p] theta[(p n_tx + a) n_rx + r]      (the effective channel),
 // in the residual form: both data terms are non-negative up to rounding (the expanded form
 // ||y||^2 - 2 Re(y^H H m) + tr(H S H^H) cancels at high SNR).  The data term separates over the
 // receive antennas, sum_r ( |y_r - h_r m|^2 + h_r C h_r^H ) with h_r row r of H_t, so one work
@@ -18,7 +18,8 @@
 //   one element, which takes the 128-byte row stride off the ds_read_b128 bank pattern.  Pilot
 //   items walk the same tiles with u_p read from global memory.
 // Determinism: no atomics.  A block's sum is the fixed-order DPP wave reduction (wave_sum_dpp),
-//   then the four wave sums added in wave order; block sums go to part[b][k]; nblk and the
+//   then the four wave sums added in wave order (block_sum4, shared with loglik.hip's pilot
+//   items); block sums go to part[b][k]; nblk and the
 //   item -> block map depend on (T_d, T_p, n_rx) only, never on B.
 // noise_final_kernel     one thread per trial: part[b][0..nblk) in index order, the floor and
 //   keep-previous rules, varn_est[b] and (optionally) varn_hist[b][it].
@@ -111,10 +112,8 @@ __global__ __launch_bounds__(kNoiseThreads) void noise_partial_kernel(NoiseArgs 
     } else if (is_p) {
         q = cabs2(csub(a.yp[((size_t)b * Tp + t) * NR + r], h[0]));
     }
-    q = wave_sum_dpp(q);
-    if ((tid & 63) == 0) red[tid >> 6] = q;
-    __syncthreads();
-    if (tid == 0) a.part[(size_t)b * a.nblk + blk] = ((red[0] + red[1]) + red[2]) + red[3];
+    q = block_sum4(wave_sum_dpp(q), red, tid & 63, tid >> 6);
+    if (tid == 0) a.part[(size_t)b * a.nblk + blk] = q;
 }
 
 __global__ __launch_bounds__(256) void noise_final_kernel(NoiseFinalArgs f) {

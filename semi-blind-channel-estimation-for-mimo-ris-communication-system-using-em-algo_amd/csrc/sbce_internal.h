@@ -24,6 +24,9 @@ typedef double2 cd;
 // drop or min-norm paths: its pivots past the numerical rank ARE the rounding noise, and the
 // pivot decisions must see four-MFMA rounding.
 typedef double mf4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ mf4 mfma4(double a, double b, mf4 c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
 template <bool G3>
 __device__ __forceinline__ void csub_init(mf4& cre, mf4& cim, mf4& c2) {
     c2 = mf4{0.0, 0.0, 0.0, 0.0};
@@ -176,6 +179,13 @@ __device__ __forceinline__ double wave_max_dpp(double v) {
     v = fmax(v, dpp_d<0x141>(v));
     v = fmax(v, dpp_d<0x140>(v));
     return fmax(fmax(lane_d(v, 0), lane_d(v, 16)), fmax(lane_d(v, 32), lane_d(v, 48)));
+}
+// The sum of a 256-thread block from its four wave sums v (wave-uniform), added in wave order;
+// red: 4 doubles of LDS.  One barrier; every thread of the block calls it.
+__device__ __forceinline__ double block_sum4(double v, double* red, int lane, int w) {
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
 }
 // a wave-uniform double moved to SGPRs (readfirstlane of both halves)
 __device__ __forceinline__ double uniform_d(double v) {
@@ -519,13 +529,13 @@ struct DetectArgs {
     double* post;      // [B][Td][NT][M] or null
     double* llr;       // [B][Td][NT][lgM] or null
     int32_t* err;      // [B][2] or null (zeroed before the launch)
-    int B, NT, NR, P, Td, M, lgM;
+    int B, NT, NR, P, Td, M;
+    int lgM;           // set by launch_detect (M is a power of two), as TC and chunks
     int maxlog;        // llr holds the max-log L-values
-    int TC, chunks;    // symbols per workgroup, workgroups per trial (set by launch_detect)
+    int TC, chunks;    // symbols per workgroup, workgroups per trial
     double sigma2;
 };
-constexpr int kDetectMaxJ = 65536;
-bool detect_supported(int NT, int NR, int M);   // 1..4, 1..8, M^NT <= kDetectMaxJ
+bool detect_supported(int NT, int NR, int M);   // hyp_enum.h's limits: 1..4, 1..8, M^NT <= 65536
 hipError_t launch_detect(DetectArgs a, hipStream_t s);
 
 // Noise-variance update (noise.hip, sbce_noise_var / sbce_em_noise): two launches per update
@@ -577,7 +587,7 @@ struct LoglikArgs {
     int npb;           // pilot workgroups per trial
     double varn;
 };
-bool loglik_supported(const Problem& pb);   // detect_supported's limits, M a power of two
+bool loglik_supported(const Problem& pb);   // hyp_enum.h's limits, M a power of two
 int loglik_npb(const Problem& pb);          // a function of (T_p, n_rx) only
 hipError_t launch_loglik(const Problem& pb, LoglikArgs a, hipStream_t s);
 

@@ -87,6 +87,87 @@ def _varn_arg(torch, varn, B):
     return float(v[0]), torch.from_numpy(v).to("cuda")
 
 
+def _cdev(torch, x):
+    """An input as a contiguous CUDA tensor: None stays None, a tensor is moved if it is not on
+    the device (a contiguous CUDA tensor is used in place), an array becomes complex128."""
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor):
+        return (x if x.is_cuda else x.to("cuda")).contiguous()
+    return _dev(torch, x, np.complex128)
+
+
+def _ptrs(t_p, **fields):
+    """_lib.Ptrs by field name: a tensor gives its data_ptr(), None (or a field left out) is
+    null, ``workspace`` also sets workspace_bytes; an unknown name raises TypeError.
+    T_p == 0 (superimposed protocol, stand-alone E-step): an empty tensor's data_ptr() is 0,
+    which the ABI rejects; the pilot buffers are never read then, so y_d stands in for both."""
+    unknown = set(fields) - {f for f, _ in _lib.Ptrs._fields_}
+    if unknown:                 # ctypes would take any keyword as a plain attribute
+        raise TypeError(f"sbce_ptrs has no field {sorted(unknown)}")
+    if not t_p:
+        fields["y_p"] = fields["u_p"] = fields["y_d"]
+    if fields.get("workspace") is not None:
+        fields["workspace_bytes"] = fields["workspace"].numel()
+    return _lib.Ptrs(**{k: v.data_ptr() if hasattr(v, "data_ptr") else v
+                        for k, v in fields.items() if v is not None})
+
+
+def _scratch(torch, query, what, *args):
+    """A device scratch buffer of the size a sbce_*_workspace_bytes entry point reports."""
+    nb = ctypes.c_size_t(0)
+    _lib.check(query(*args, ctypes.byref(nb)), what)
+    return torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+
+
+class _Staged:
+    """One problem on the device: the six input tensors, Dims, workspace, status and iters_done.
+
+    check: the name of the theta argument in the shape errors of the batched entry points; None
+    (the diagnostic stages) leaves every validation to the library.  clone: theta is a private
+    copy of the input (theta0 keeps the input).  workspace: False for none, else the sbce_em
+    workspace for the SBCE_SOLVE_* mode ``solve`` (None: for every mode)."""
+
+    def __init__(self, torch, y_d, y_p, psi_d, u_p, cons, theta, varn, partition_r=0, varx=1.0,
+                 solve=None, check=None, clone=False, workspace=True):
+        self.y_d, self.y_p, self.psi_d, self.u_p, self.cons, self.theta0 = (
+            _cdev(torch, x) for x in (y_d, y_p, psi_d, u_p, cons, theta))
+        self.theta = self.theta0.clone() if clone else self.theta0
+        B, T_d, n_rx = self.y_d.shape
+        T_p, P, L = self.y_p.shape[1], self.psi_d.shape[2], self.u_p.shape[2]
+        self.B, self.T_d, self.n_rx, self.T_p, self.P = B, T_d, n_rx, T_p, P
+        if check and L % P:
+            raise ValueError("u_p width must be P*n_tx")
+        self.n_tx, self.M = L // P, self.cons.shape[0]
+        if check and self.theta.shape != (B, L * n_rx):
+            raise ValueError(f"{check} shape {tuple(self.theta.shape)} != {(B, L * n_rx)}")
+        self.varn, self.varn_t = _varn_arg(torch, varn, B) if check else (float(varn), None)
+        self.dims = _lib.Dims(B, self.n_tx, n_rx, P, T_p, T_d, self.M, int(partition_r), self.varn,
+                              float(varx))
+        self.ws = (torch.empty(max(_lib.workspace_bytes(self.dims, solve), 16), dtype=torch.uint8,
+                               device="cuda") if workspace else None)
+        self.status = torch.zeros(B, dtype=torch.int32, device="cuda")
+        self.iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
+
+    def ptrs(self, rows=slice(None), ws=None, **per_trial):
+        """sbce_ptrs of the trials ``rows`` (a slice; default: all) with the workspace ``ws``
+        (default: the problem's own); per_trial: further batch-major tensors by field name
+        (x_d_true, llf, h_true, x_dest, x_sup), None for absent."""
+        per_trial.update(y_d=self.y_d, y_p=self.y_p, psi_d=self.psi_d, u_p=self.u_p,
+                         theta=self.theta, iters_done=self.iters_done, status=self.status,
+                         varn_t=self.varn_t)
+        views = {k: v[rows] for k, v in per_trial.items() if v is not None}
+        return _ptrs(self.T_p, cons=self.cons, workspace=self.ws if ws is None else ws, **views)
+
+
+def _result(torch, out, return_device):
+    """The result dict as it is (device tensors), or synchronised and copied to numpy."""
+    if return_device:
+        return out
+    torch.cuda.current_stream().synchronize()
+    return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+
+
 def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_true=None,
              h_true=None, solve="chol", return_device=False, partition_r=0,
              return_decisions=False, x_sup=None, varx=1.0):
@@ -112,57 +193,21 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
     """
     torch = _torch()
     lib = _lib.load()
-
-    def dev(x):
-        if x is None:
-            return None
-        if isinstance(x, torch.Tensor):
-            t = x if x.is_cuda else x.to("cuda")
-            return t.contiguous()
-        return _dev(torch, x, np.complex128)
-
-    Yd, Yp, Ps, Up, Cs = dev(y_d), dev(y_p), dev(psi_d), dev(u_p), dev(cons)
-    th = dev(theta0).clone()
-    B, T_d, n_rx = Yd.shape
-    T_p = Yp.shape[1]
-    P = Ps.shape[2]
-    L = Up.shape[2]
-    if L % P:
-        raise ValueError("u_p width must be P*n_tx")
-    n_tx = L // P
-    M = Cs.shape[0]
-    if th.shape != (B, L * n_rx):
-        raise ValueError(f"theta0 shape {tuple(th.shape)} != {(B, L * n_rx)}")
-    varn0, Vt = _varn_arg(torch, varn, B)
-    dims = _lib.Dims(B, n_tx, n_rx, P, T_p, T_d, M, int(partition_r), varn0, float(varx))
-    ws_bytes = _lib.workspace_bytes(dims, _SOLVES[solve])
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device="cuda")
-    status = torch.zeros(B, dtype=torch.int32, device="cuda")
-    iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
-    Xd = dev(x_d_true)
-    Ht = dev(h_true)
-    llf = torch.zeros((B, max(itera, 1)), dtype=torch.float64, device="cuda") if Xd is not None else None
-    xdest = (torch.zeros((B, T_d, n_tx), dtype=torch.complex128, device="cuda")
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn, partition_r, varx,
+                 solve=_SOLVES[solve], check="theta0", clone=True)
+    Xd, Ht, Xs = (_cdev(torch, x) for x in (x_d_true, h_true, x_sup))
+    llf = (torch.zeros((st.B, max(itera, 1)), dtype=torch.float64, device="cuda")
+           if Xd is not None else None)
+    xdest = (torch.zeros((st.B, st.T_d, st.n_tx), dtype=torch.complex128, device="cuda")
              if return_decisions else None)
-    Xs = dev(x_sup)
-    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
-                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), th.data_ptr(),
-                     Xd.data_ptr() if Xd is not None else None,
-                     llf.data_ptr() if llf is not None else None,
-                     Ht.data_ptr() if Ht is not None else None, iters_done.data_ptr(),
-                     status.data_ptr(), ws.data_ptr(), ws.numel(),
-                     xdest.data_ptr() if xdest is not None else None,
-                     Xs.data_ptr() if Xs is not None else None,
-                     Vt.data_ptr() if Vt is not None else None)
+    ptrs = st.ptrs(x_d_true=Xd, llf=llf, h_true=Ht, x_dest=xdest, x_sup=Xs)
     stream = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.sbce_em(dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve], stream), "sbce_em")
-    out = dict(theta=th, llf=llf, status=status, iters_done=iters_done)
+    _lib.check(lib.sbce_em(st.dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve], stream),
+               "sbce_em")
+    out = dict(theta=st.theta, llf=llf, status=st.status, iters_done=st.iters_done)
     if xdest is not None:
         out["x_dest"] = xdest
-    if return_device:
-        return out
-    torch.cuda.current_stream().synchronize()
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+    return _result(torch, out, return_device)
 
 
 _NOISE_MODES = ("soft", "hard", "pm", "pm_soft", "zf", "mmse")
@@ -178,11 +223,16 @@ def _noise_checks(mode, varn_min):
     return vmin
 
 
-def _noise_scratch(torch, lib, dims):
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.sbce_noise_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
-               "sbce_noise_workspace_bytes")
-    return torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+def _noise_opts(torch, lib, st, vmin, iters=0):
+    """sbce_noise_opts for the staged problem: (opts, varn_est (B,), varn_hist (B,iters) or None
+    when iters == 0, the scratch buffer the caller keeps alive)."""
+    scratch = _scratch(torch, lib.sbce_noise_workspace_bytes, "sbce_noise_workspace_bytes",
+                       ctypes.byref(st.dims))
+    est = torch.zeros(st.B, dtype=torch.float64, device="cuda")
+    hist = torch.zeros((st.B, iters), dtype=torch.float64, device="cuda") if iters else None
+    opts = _lib.NoiseOpts(est.data_ptr(), hist.data_ptr() if iters else None, scratch.data_ptr(),
+                          scratch.numel(), vmin, 0)
+    return opts, est, hist, scratch
 
 
 def noise_var_batch(y_d, y_p, psi_d, u_p, theta, m, S, varn_min=1e-6, return_status=False):
@@ -201,19 +251,17 @@ def noise_var_batch(y_d, y_p, psi_d, u_p, theta, m, S, varn_min=1e-6, return_sta
         raise ValueError("u_p width must be P*n_tx")
     torch = _torch()
     lib = _lib.load()
-    dims, ptrs, keep = _stage_setup(torch, y_d, y_p, psi_d, u_p, np.ones(2, dtype=complex), theta,
-                                    1.0, workspace=False)
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, np.ones(2, dtype=complex), theta, 1.0,
+                 workspace=False)
     mom = _dev(torch, np.concatenate([np.asarray(m).reshape(B, T_d, n_tx),
                                       np.asarray(S).reshape(B, T_d, n_tx * n_tx)], axis=2),
                np.complex128)
-    est = torch.zeros(B, dtype=torch.float64, device="cuda")
-    scratch = _noise_scratch(torch, lib, dims)
-    opts = _lib.NoiseOpts(est.data_ptr(), None, scratch.data_ptr(), scratch.numel(), vmin, 0)
-    _lib.check(lib.sbce_noise_var(dims, ptrs, mom.data_ptr(), opts,
+    opts, est, _, scratch = _noise_opts(torch, lib, st, vmin)
+    _lib.check(lib.sbce_noise_var(st.dims, st.ptrs(), mom.data_ptr(), opts,
                                   torch.cuda.current_stream().cuda_stream), "sbce_noise_var")
     torch.cuda.current_stream().synchronize()
     v = est.cpu().numpy()
-    return (v * v, keep[7].cpu().numpy()) if return_status else v * v
+    return (v * v, st.status.cpu().numpy()) if return_status else v * v
 
 
 def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", solve="chol",
@@ -235,55 +283,16 @@ def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft",
         raise ValueError("itera must be >= 1")
     torch = _torch()
     lib = _lib.load()
-
-    def dev(x):
-        if x is None:
-            return None
-        if isinstance(x, torch.Tensor):
-            return (x if x.is_cuda else x.to("cuda")).contiguous()
-        return _dev(torch, x, np.complex128)
-
-    Yd, Yp, Ps, Up, Cs = dev(y_d), dev(y_p), dev(psi_d), dev(u_p), dev(cons)
-    th = dev(theta0).clone()
-    B, T_d, n_rx = Yd.shape
-    T_p, P, L = Yp.shape[1], Ps.shape[2], Up.shape[2]
-    if L % P:
-        raise ValueError("u_p width must be P*n_tx")
-    n_tx = L // P
-    if th.shape != (B, L * n_rx):
-        raise ValueError(f"theta0 shape {tuple(th.shape)} != {(B, L * n_rx)}")
-    varn0, Vt = _varn_arg(torch, varn, B)
-    dims = _lib.Dims(B, n_tx, n_rx, P, T_p, T_d, Cs.shape[0], int(partition_r), varn0, 1.0)
-    ws = torch.empty(max(_lib.workspace_bytes(dims, _SOLVES[solve]), 16), dtype=torch.uint8,
-                     device="cuda")
-    scratch = _noise_scratch(torch, lib, dims)
-    status = torch.zeros(B, dtype=torch.int32, device="cuda")
-    iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
-    est = torch.zeros(B, dtype=torch.float64, device="cuda")
-    hist = torch.zeros((B, int(itera)), dtype=torch.float64, device="cuda")
-    Ht = dev(h_true)
-    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
-                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), th.data_ptr(), None,
-                     None, Ht.data_ptr() if Ht is not None else None, iters_done.data_ptr(),
-                     status.data_ptr(), ws.data_ptr(), ws.numel(), None, None,
-                     Vt.data_ptr() if Vt is not None else None)
-    opts = _lib.NoiseOpts(est.data_ptr(), hist.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                          vmin, 0)
-    _lib.check(lib.sbce_em_noise(dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve], opts,
-                                 torch.cuda.current_stream().cuda_stream), "sbce_em_noise")
-    out = dict(theta=th, varn=est, sigma2=est * est, hist=hist, status=status,
-               iters_done=iters_done)
-    if return_device:
-        return out
-    torch.cuda.current_stream().synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _scratch(torch, query, what, *args):
-    """A device scratch buffer of the size a sbce_*_workspace_bytes entry point reports."""
-    nb = ctypes.c_size_t(0)
-    _lib.check(query(*args, ctypes.byref(nb)), what)
-    return torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn, partition_r,
+                 solve=_SOLVES[solve], check="theta0", clone=True)
+    opts, est, hist, scratch = _noise_opts(torch, lib, st, vmin, int(itera))
+    Ht = _cdev(torch, h_true)
+    _lib.check(lib.sbce_em_noise(st.dims, st.ptrs(h_true=Ht), int(itera), _MODES[mode],
+                                 _SOLVES[solve], opts, torch.cuda.current_stream().cuda_stream),
+               "sbce_em_noise")
+    out = dict(theta=st.theta, varn=est, sigma2=est * est, hist=hist, status=st.status,
+               iters_done=st.iters_done)
+    return _result(torch, out, return_device)
 
 
 def loglik_batch(y_d, y_p, psi_d, u_p, cons, theta, varn, n_tx, per_symbol=False):
@@ -297,23 +306,13 @@ def loglik_batch(y_d, y_p, psi_d, u_p, cons, theta, varn, n_tx, per_symbol=False
         raise ValueError("u_p width must be P*n_tx")
     torch = _torch()
     lib = _lib.load()
-    Yd, Yp, Ps, Up, Cs, Th = (_dev(torch, x, np.complex128)
-                              for x in (y_d, y_p, psi_d, u_p, cons, theta))
-    B, T_d, n_rx = Yd.shape
-    T_p, P = Yp.shape[1], Ps.shape[2]
-    if Th.shape != (B, P * int(n_tx) * n_rx):
-        raise ValueError(f"theta shape {tuple(Th.shape)} != {(B, P * int(n_tx) * n_rx)}")
-    varn0, Vt = _varn_arg(torch, varn, B)
-    dims = _lib.Dims(B, int(n_tx), n_rx, P, T_p, T_d, Cs.shape[0], 0, varn0, 1.0)
-    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
-                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), Th.data_ptr(), None,
-                     None, None, None, None, None, 0, None, None,
-                     Vt.data_ptr() if Vt is not None else None)
-    ll = torch.zeros(B, dtype=torch.float64, device="cuda")
-    sym = torch.zeros((B, T_d), dtype=torch.float64, device="cuda") if per_symbol else None
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta, varn, check="theta", workspace=False)
+    ll = torch.zeros(st.B, dtype=torch.float64, device="cuda")
+    sym = torch.zeros((st.B, st.T_d), dtype=torch.float64, device="cuda") if per_symbol else None
     scratch = _scratch(torch, lib.sbce_loglik_workspace_bytes, "sbce_loglik_workspace_bytes",
-                       ctypes.byref(dims))
-    _lib.check(lib.sbce_loglik(dims, ptrs, ll.data_ptr(), sym.data_ptr() if per_symbol else None,
+                       ctypes.byref(st.dims))
+    _lib.check(lib.sbce_loglik(st.dims, st.ptrs(), ll.data_ptr(),
+                               sym.data_ptr() if per_symbol else None,
                                scratch.data_ptr(), scratch.numel(),
                                torch.cuda.current_stream().cuda_stream), "sbce_loglik")
     torch.cuda.current_stream().synchronize()
@@ -351,55 +350,28 @@ def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta
     vmin = _noise_checks(mode, varn_min)
     torch = _torch()
     lib = _lib.load()
-
-    def dev(x):
-        if isinstance(x, torch.Tensor):
-            return (x if x.is_cuda else x.to("cuda")).contiguous()
-        return _dev(torch, x, np.complex128)
-
-    Yd, Yp, Ps, Up, Cs = dev(y_d), dev(y_p), dev(psi_d), dev(u_p), dev(cons)
-    th = dev(theta0).clone()
-    B, T_d, n_rx = Yd.shape
-    T_p, P, L = Yp.shape[1], Ps.shape[2], Up.shape[2]
-    if L % P:
-        raise ValueError("u_p width must be P*n_tx")
-    n_tx = L // P
-    if th.shape != (B, L * n_rx):
-        raise ValueError(f"theta0 shape {tuple(th.shape)} != {(B, L * n_rx)}")
-    varn0, Vt = _varn_arg(torch, varn, B)
-    dims = _lib.Dims(B, n_tx, n_rx, P, T_p, T_d, Cs.shape[0], int(partition_r), varn0, 1.0)
-    ws = torch.empty(max(_lib.workspace_bytes(dims, _SOLVES[solve]), 16), dtype=torch.uint8,
-                     device="cuda")
-    status = torch.zeros(B, dtype=torch.int32, device="cuda")
-    iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn, partition_r,
+                 solve=_SOLVES[solve], check="theta0", clone=True)
+    B = st.B
     dth = torch.zeros((B, iters), dtype=torch.float64, device="cuda")
     llh = torch.zeros((B, iters), dtype=torch.float64, device="cuda") if loglik else None
     cscratch = _scratch(torch, lib.sbce_conv_workspace_bytes, "sbce_conv_workspace_bytes",
-                        ctypes.byref(dims), 1 if loglik else 0)
-    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
-                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), th.data_ptr(), None,
-                     None, None, iters_done.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                     ws.numel(), None, None, Vt.data_ptr() if Vt is not None else None)
+                        ctypes.byref(st.dims), 1 if loglik else 0)
     cv = _lib.ConvOpts(tt, tl, mi, 0, dth.data_ptr(), llh.data_ptr() if loglik else None,
                        cscratch.data_ptr(), cscratch.numel())
-    nz, est, hist = None, None, None
+    nz, hist = None, None
     if estimate_noise:
-        nscratch = _noise_scratch(torch, lib, dims)
-        est = torch.zeros(B, dtype=torch.float64, device="cuda")
-        hist = torch.zeros((B, iters), dtype=torch.float64, device="cuda")
-        nz = _lib.NoiseOpts(est.data_ptr(), hist.data_ptr(), nscratch.data_ptr(), nscratch.numel(),
-                            vmin, 0)
+        nz, est, hist, nscratch = _noise_opts(torch, lib, st, vmin, iters)
+    elif st.varn_t is not None:
+        est = st.varn_t
     else:
-        est = Vt if Vt is not None else torch.full((B,), varn0, dtype=torch.float64, device="cuda")
-    _lib.check(lib.sbce_em_conv(dims, ptrs, iters, _MODES[mode], _SOLVES[solve],
+        est = torch.full((B,), st.varn, dtype=torch.float64, device="cuda")
+    _lib.check(lib.sbce_em_conv(st.dims, st.ptrs(), iters, _MODES[mode], _SOLVES[solve],
                                 ctypes.byref(nz) if nz is not None else None, ctypes.byref(cv),
                                 torch.cuda.current_stream().cuda_stream), "sbce_em_conv")
-    out = dict(theta=th, iters_done=iters_done, status=status, dtheta_hist=dth, ll_hist=llh,
-               varn=est, sigma2=est * est, hist=hist)
-    if return_device:
-        return out
-    torch.cuda.current_stream().synchronize()
-    return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+    out = dict(theta=st.theta, iters_done=st.iters_done, status=st.status, dtheta_hist=dth,
+               ll_hist=llh, varn=est, sigma2=est * est, hist=hist)
+    return _result(torch, out, return_device)
 
 
 def _prepare_single(Y_d, Y_p, Z_p, PsiTilde_td, all_possibleSymbols, M, h_initial, n_tx=None,
@@ -697,14 +669,8 @@ def em_approx_batch(y_d, y_p, psi_d, psi_p, x_p, varn, updates, g0, return_devic
     and keeps its last finite iterate."""
     torch = _torch()
     lib = _lib.load()
-
-    def dev(x):
-        if isinstance(x, torch.Tensor):
-            return (x if x.is_cuda else x.to("cuda")).contiguous()
-        return _dev(torch, x, np.complex128)
-
-    Yd, Yp, Pd, Pp, Xp = dev(y_d), dev(y_p), dev(psi_d), dev(psi_p), dev(x_p)
-    G = dev(g0).clone()
+    Yd, Yp, Pd, Pp, Xp = (_cdev(torch, x) for x in (y_d, y_p, psi_d, psi_p, x_p))
+    G = _cdev(torch, g0).clone()
     B, T_d, n_rx = Yd.shape
     T_p, N = Pp.shape[1], Pd.shape[2]
     if (Yp.shape != (B, T_p, n_rx) or Pd.shape != (B, T_d, N) or Pp.shape != (B, T_p, N)
@@ -712,21 +678,15 @@ def em_approx_batch(y_d, y_p, psi_d, psi_p, x_p, varn, updates, g0, return_devic
         raise ValueError("em_approx_batch: inconsistent shapes")
     varn0, Vt = _varn_arg(torch, varn, B)
     dims = _lib.ApproxDims(B, N, n_rx, T_p, T_d, 0, varn0)
-    nb = ctypes.c_size_t(0)
-    _lib.check(lib.sbce_approx_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
-               "sbce_approx_workspace_bytes")
-    ws = torch.empty(max(nb.value, 16), dtype=torch.uint8, device="cuda")
+    ws = _scratch(torch, lib.sbce_approx_workspace_bytes, "sbce_approx_workspace_bytes",
+                  ctypes.byref(dims))
     status = torch.zeros(B, dtype=torch.int32, device="cuda")
     ptrs = _lib.ApproxPtrs(Yd.data_ptr(), Yp.data_ptr(), Pd.data_ptr(), Pp.data_ptr(),
                            Xp.data_ptr(), G.data_ptr(), Vt.data_ptr() if Vt is not None else None,
                            status.data_ptr(), ws.data_ptr(), ws.numel())
     _lib.check(lib.sbce_approx_em(dims, ptrs, int(updates),
                                   torch.cuda.current_stream().cuda_stream), "sbce_approx_em")
-    out = dict(g=G, status=status)
-    if return_device:
-        return out
-    torch.cuda.current_stream().synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return _result(torch, dict(g=G, status=status), return_device)
 
 
 def EM_approx(PsiTilde_tp, PsiTilde_td, x_p, Y_p, Y_d, Iterations, varn, G=None, verbose=False):
@@ -815,10 +775,11 @@ def _detect_call(torch, Yd, Ps, Cs, Th, n_tx, sigma2, sigma2_t, lab, Xd, maxlog,
 
 def _sigma2_arg(torch, varn, B, noise):
     """(dims.sigma2, per-trial device tensor or None): the posterior denominator, varn**2 for the
-    EM posterior (noise='em') or varn itself, the noise the data were drawn with (noise='true')."""
+    EM posterior (noise='em') or varn itself, the noise the data were drawn with (noise='true').
+    varn: one value, a (B,) array, or the pair _varn_arg already made of one (EMEngine)."""
     if noise not in ("em", "true"):
         raise ValueError("noise must be 'em' or 'true'")
-    v0, Vt = _varn_arg(torch, varn, B)
+    v0, Vt = varn if isinstance(varn, tuple) else _varn_arg(torch, varn, B)
     if noise == "em":
         return v0 * v0, (Vt * Vt if Vt is not None else None)
     return v0, Vt
@@ -839,23 +800,12 @@ def detect_batch(y_d, psi_d, cons, theta, varn, n_tx, labels=None, x_d_true=None
     (B,T_d,n_tx,log2 M) L-values log(p0/p1), exact or (maxlog=True) max-log; with x_d_true
     also err (B,2) int32 = per-trial symbol and bit error counts."""
     torch = _torch()
-
-    def dev(x):
-        if x is None:
-            return None
-        if isinstance(x, torch.Tensor):
-            return (x if x.is_cuda else x.to("cuda")).contiguous()
-        return _dev(torch, x, np.complex128)
-
-    Yd, Ps, Cs, Th, Xd = dev(y_d), dev(psi_d), dev(cons), dev(theta), dev(x_d_true)
+    Yd, Ps, Cs, Th, Xd = (_cdev(torch, x) for x in (y_d, psi_d, cons, theta, x_d_true))
     lab = _detect_labels(Cs.shape[0], labels, "llr" in want or Xd is not None)
     lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
     s2, s2t = _sigma2_arg(torch, varn, Yd.shape[0], noise)
     out = _detect_call(torch, Yd, Ps, Cs, Th, int(n_tx), s2, s2t, lab_d, Xd, maxlog, tuple(want))
-    if return_device:
-        return out
-    torch.cuda.current_stream().synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return _result(torch, out, return_device)
 
 
 def detect(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, labels=None, X_d=None,
@@ -898,26 +848,6 @@ def em_zero_init(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, v
 
 
 # ------------------------------------------------------------------ diagnostic stages
-def _stage_setup(torch, y_d, y_p, psi_d, u_p, cons, theta, varn, partition_r=0, varx=1.0,
-                 workspace=True):
-    def dev(x):
-        return _dev(torch, x, np.complex128)
-    Yd, Yp, Ps, Up, Cs, Th = (dev(y_d), dev(y_p), dev(psi_d), dev(u_p), dev(cons), dev(theta))
-    B, T_d, n_rx = Yd.shape
-    T_p, P, L = Yp.shape[1], Ps.shape[2], Up.shape[2]
-    n_tx = L // P
-    dims = _lib.Dims(B, n_tx, n_rx, P, T_p, T_d, Cs.shape[0], int(partition_r), float(varn),
-                     float(varx))
-    ws = torch.empty(max(_lib.workspace_bytes(dims), 16), dtype=torch.uint8, device="cuda")
-    status = torch.zeros(B, dtype=torch.int32, device="cuda")
-    ptrs = _lib.Ptrs(Yd.data_ptr(), Yp.data_ptr() if T_p else Yd.data_ptr(), Ps.data_ptr(),
-                     Up.data_ptr() if T_p else Yd.data_ptr(), Cs.data_ptr(), Th.data_ptr(), None,
-                     None, None, None, status.data_ptr(), ws.data_ptr() if workspace else None,
-                     ws.numel() if workspace else 0)
-    keep = (Yd, Yp, Ps, Up, Cs, Th, ws, status)
-    return dims, ptrs, keep
-
-
 def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0, varx=1.0,
                 workspace=True):
     """One device E-step (sbce_estep): returns m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx).
@@ -929,11 +859,12 @@ def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0,
     P = np.shape(psi_d)[2]
     y_p = np.zeros((B, 0, n_rx), dtype=complex)
     u_p = np.zeros((B, 0, P * n_tx), dtype=complex)
-    dims, ptrs, keep = _stage_setup(torch, y_d, y_p, psi_d, u_p, cons, theta, varn, partition_r,
-                                    varx, workspace)
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta, varn, partition_r, varx,
+                 workspace=workspace)
     mom = torch.zeros((B, T_d, n_tx + n_tx * n_tx), dtype=torch.complex128, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.sbce_estep(dims, ptrs, _MODES[mode], mom.data_ptr(), stream), "sbce_estep")
+    _lib.check(lib.sbce_estep(st.dims, st.ptrs(), _MODES[mode], mom.data_ptr(), stream),
+               "sbce_estep")
     torch.cuda.current_stream().synchronize()
     mom = mom.cpu().numpy()
     return mom[..., :n_tx], mom[..., n_tx:].reshape(B, T_d, n_tx, n_tx)
@@ -952,9 +883,10 @@ def mstep_batch(y_d, y_p, psi_d, u_p, cons, m, S, varn, solve="chol", return_tol
     L = np.shape(u_p)[2]
     n_tx = np.shape(m)[2]
     theta = np.zeros((B, L * n_rx), dtype=complex)
-    dims, ptrs, keep = _stage_setup(torch, y_d, y_p, psi_d, u_p, cons, theta, varn)
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta, varn)
+    dims, ptrs = st.dims, st.ptrs()
     if ws_fill is not None:
-        keep[6].fill_(int(ws_fill))
+        st.ws.fill_(int(ws_fill))
     mom = np.concatenate([np.asarray(m).reshape(B, T_d, n_tx),
                           np.asarray(S).reshape(B, T_d, n_tx * n_tx)], axis=2)
     Mo = _dev(torch, mom, np.complex128)
@@ -972,12 +904,12 @@ def mstep_batch(y_d, y_p, psi_d, u_p, cons, m, S, varn, solve="chol", return_tol
         _lib.check(fn(ctypes.byref(dims), ctypes.byref(ptrs), tol.ctypes.data_as(ctypes.c_void_p),
                       ctypes.c_void_p(stream)), "sbce_debug_minnorm_tol")
     torch.cuda.current_stream().synchronize()
-    th = keep[5].cpu().numpy()
+    th = st.theta.cpu().numpy()
     # the device keeps only R's lower triangle (its strict upper part is factorisation
     # workspace): return the Hermitian completion
     R = np.tril(R.cpu().numpy())
     R = R + np.conj(np.swapaxes(np.tril(R, -1), 1, 2))
-    out = (th, R, rhs.cpu().numpy(), keep[7].cpu().numpy())
+    out = (th, R, rhs.cpu().numpy(), st.status.cpu().numpy())
     return out + (tol,) if return_tol else out
 
 
@@ -1020,31 +952,20 @@ class EMEngine:
         the iterations each trial of the last run() performed."""
         torch = _torch()
         self.torch = torch
-
-        def dev(x):
-            if x is None:
-                return None
-            if isinstance(x, torch.Tensor):
-                return x.to("cuda").contiguous()
-            return _dev(torch, x, np.complex128)
-
-        self.y_d, self.y_p = dev(batch["y_d"]), dev(batch["y_p"])
-        self.psi_d, self.u_p = dev(batch["psi_d"]), dev(batch["u_p"])
-        self.cons, self.theta0 = dev(batch["cons"]), dev(batch["theta0"])
-        self.h = dev(h_true if h_true is not None else batch.get("h"))
-        self.theta = self.theta0.clone()
-        B, T_d, n_rx = self.y_d.shape
-        T_p, P, L = self.y_p.shape[1], self.psi_d.shape[2], self.u_p.shape[2]
-        self.n_tx, self.n_rx, self.B, self.T_d, self.T_p, self.P = L // P, n_rx, B, T_d, T_p, P
-        self.M = self.cons.shape[0]
-        # one noise variance, or one per trial (the SNR axis of a sweep batched into one call)
-        self.varn, self.varn_t = _varn_arg(torch, varn, B)
+        # varn: one noise variance, or one per trial (the SNR axis of a sweep batched into one
+        # call).  The engine owns the workspace (below): the staged problem gets none of its own.
+        st = _Staged(torch, batch["y_d"], batch["y_p"], batch["psi_d"], batch["u_p"], batch["cons"],
+                     batch["theta0"], varn, partition_r, varx, check="theta0", clone=True,
+                     workspace=False)
+        for k in ("y_d", "y_p", "psi_d", "u_p", "cons", "theta0", "theta", "n_tx", "n_rx", "B",
+                  "T_d", "T_p", "P", "M", "varn", "varn_t", "dims", "status", "iters_done"):
+            setattr(self, k, getattr(st, k))
+        B, T_d, n_rx, T_p, P = st.B, st.T_d, st.n_rx, st.T_p, st.P
+        self.h = _cdev(torch, h_true if h_true is not None else batch.get("h"))
         if mode == "gauss" and not varx > 0:
             raise ValueError("mode 'gauss' needs a prior variance varx > 0")
         if x_sup is not None and mode not in ("soft", "hard"):
             raise ValueError("superimposed pilots (x_sup) need the soft or hard E-step")
-        self.dims = _lib.Dims(B, self.n_tx, n_rx, P, T_p, T_d, self.M, int(partition_r), self.varn,
-                              float(varx))
         self.mode, self.solve = _MODES[mode], _SOLVES[solve]
         # ONE device buffer: the whole-batch workspace (estep / mstep / mstep_phase) and, when the
         # batch runs as stream sub-batches, their workspaces as disjoint slices of the same memory
@@ -1059,26 +980,15 @@ class EMEngine:
         self.ws_all = torch.empty(max(whole, sum(sub_bytes) if sub else 0, 16), dtype=torch.uint8,
                                   device="cuda")
         self.ws = self.ws_all[:max(whole, 16)]
-        self.status = torch.zeros(B, dtype=torch.int32, device="cuda")
-        self.x_d = dev(x_d_true)
+        self.x_d = _cdev(torch, x_d_true)
         self.mom = torch.zeros((B, T_d, self.n_tx + self.n_tx ** 2), dtype=torch.complex128,
                                device="cuda")
-        self.x_sup = dev(x_sup)
-        # T_p == 0 (superimposed protocol): an empty tensor's data_ptr() is 0, which the ABI
-        # rejects; the pilot buffers are never read then, so pass y_d as a placeholder (em_batch)
-        yp = self.y_p.data_ptr() if T_p else self.y_d.data_ptr()
-        up = self.u_p.data_ptr() if T_p else self.y_d.data_ptr()
+        self.x_sup = _cdev(torch, x_sup)
         if early_stop and self.h is None:
             raise ValueError("early_stop needs the true channel (h_true or batch['h'])")
         self.early_stop = bool(early_stop)
-        self.iters_done = torch.zeros(B, dtype=torch.int32, device="cuda")
-        hp = self.h.data_ptr() if self.early_stop else None
-        self.ptrs = _lib.Ptrs(self.y_d.data_ptr(), yp, self.psi_d.data_ptr(), up,
-                              self.cons.data_ptr(), self.theta.data_ptr(), None, None, hp,
-                              self.iters_done.data_ptr(), self.status.data_ptr(), self.ws.data_ptr(),
-                              self.ws.numel(), None,
-                              self.x_sup.data_ptr() if self.x_sup is not None else None,
-                              self.varn_t.data_ptr() if self.varn_t is not None else None)
+        hp = self.h if self.early_stop else None
+        self.ptrs = st.ptrs(ws=self.ws, h_true=hp, x_sup=self.x_sup)
         self.subs = []
         self._minnorm_ws = False        # the workspace holds a whole-batch min-norm M-step
         if sub:
@@ -1086,13 +996,7 @@ class EMEngine:
             for (b0, b1), dims, nb in zip(zip(bounds[:-1], bounds[1:]), sub_dims, sub_bytes):
                 ws = self.ws_all[off:off + nb]
                 off += nb
-                ptrs = _lib.Ptrs(self.y_d[b0:b1].data_ptr(), self.y_p[b0:b1].data_ptr(),
-                                 self.psi_d[b0:b1].data_ptr(), self.u_p[b0:b1].data_ptr(),
-                                 self.cons.data_ptr(), self.theta[b0:b1].data_ptr(), None, None,
-                                 self.h[b0:b1].data_ptr() if self.early_stop else None,
-                                 self.iters_done[b0:b1].data_ptr(), self.status[b0:b1].data_ptr(),
-                                 ws.data_ptr(), ws.numel(), None, None,
-                                 self.varn_t[b0:b1].data_ptr() if self.varn_t is not None else None)
+                ptrs = st.ptrs(slice(int(b0), int(b1)), ws=ws, h_true=hp)
                 self.subs.append((dims, ptrs, ws, torch.cuda.Stream()))
 
     def run(self, itera, stream=None):
@@ -1170,24 +1074,13 @@ class EMEngine:
         run(): the estimate; before: theta0), on the current stream: the outputs of detect_batch.
         x_d_true defaults to the engine's own (error counters when it has one)."""
         torch = self.torch
-        xd = self.x_d if x_d_true is None else (
-            x_d_true.to("cuda").contiguous() if isinstance(x_d_true, torch.Tensor)
-            else _dev(torch, x_d_true, np.complex128))
+        xd = self.x_d if x_d_true is None else _cdev(torch, x_d_true)
         lab = _detect_labels(self.M, labels, "llr" in want or xd is not None)
         lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
-        vt = self.varn_t
-        if noise == "em":
-            s2, s2t = self.varn * self.varn, (vt * vt if vt is not None else None)
-        elif noise == "true":
-            s2, s2t = self.varn, vt
-        else:
-            raise ValueError("noise must be 'em' or 'true'")
+        s2, s2t = _sigma2_arg(torch, (self.varn, self.varn_t), self.B, noise)
         out = _detect_call(torch, self.y_d, self.psi_d, self.cons, self.theta, self.n_tx, s2, s2t,
                            lab_d, xd, maxlog, tuple(want))
-        if return_device:
-            return out
-        torch.cuda.current_stream().synchronize()
-        return {k: v.cpu().numpy() for k, v in out.items()}
+        return _result(torch, out, return_device)
 
     def nmse(self):
         """Per-trial NMSE of the current theta against h (device, sbce_nmse)."""

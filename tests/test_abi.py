@@ -152,6 +152,36 @@ def test_workspace_and_validation_without_gpu(sbce):
     assert lib.sbce_em(ctypes.byref(d), ctypes.byref(p), 1, 0, L.SBCE_SOLVE_MINNORM, None) == -4
 
 
+def test_ptrs_are_built_by_field_name(sbce):
+    """em._ptrs, the one builder of sbce_ptrs: every field can be set by its name (from a tensor's
+    data_ptr() or a plain value), an unknown name raises, fields left out are null, and with
+    T_p = 0 both pilot slots hold the y_d address (an empty tensor's data_ptr() is 0, which the
+    ABI rejects)."""
+    import importlib
+    import torch
+    L = sbce._lib
+    em = importlib.import_module(sbce.__name__ + ".em")    # sbce.em is the function em()
+    names = [f for f, _ in L.Ptrs._fields_]
+    t = {f: torch.zeros(4, dtype=torch.complex128) for f in names if f != "workspace_bytes"}
+    assert len({v.data_ptr() for v in t.values()}) == len(t)
+    p = em._ptrs(1, **t)
+    for f in t:
+        assert getattr(p, f) == t[f].data_ptr(), f
+    assert p.workspace_bytes == t["workspace"].numel()
+    p = em._ptrs(1, y_d=t["y_d"], theta=4096, workspace_bytes=77)
+    assert (p.y_d, p.theta, p.workspace_bytes) == (t["y_d"].data_ptr(), 4096, 77)
+    for f in names:
+        if f not in ("y_d", "theta", "workspace_bytes"):
+            assert not getattr(p, f), f                # None (pointers) or 0
+    with pytest.raises(TypeError):
+        em._ptrs(1, y_d=t["y_d"], y_q=t["y_p"])
+    empty = torch.zeros((3, 0, 2), dtype=torch.complex128)
+    p = em._ptrs(0, y_d=t["y_d"], y_p=empty, u_p=empty, psi_d=t["psi_d"])
+    assert p.y_p == p.u_p == p.y_d == t["y_d"].data_ptr() and p.psi_d == t["psi_d"].data_ptr()
+    p = em._ptrs(2, y_d=t["y_d"], y_p=t["y_p"], u_p=t["u_p"])
+    assert (p.y_p, p.u_p) == (t["y_p"].data_ptr(), t["u_p"].data_ptr())
+
+
 def test_product_path_fails_loudly_without_gpu(sbce):
     import torch
     if torch.cuda.is_available():
