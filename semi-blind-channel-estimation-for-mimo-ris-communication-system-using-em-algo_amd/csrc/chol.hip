@@ -1467,11 +1467,137 @@ __device__ __forceinline__ void bs3_step(int kb, int L, int tid, int lane, int w
     __syncthreads();
 }
 
+// Remainder fold: the last block of the back substitution (columns k0 .. L-1, w = L - k0 <= 4) is
+// still unfactored.  Thread tid holds l_i,tid = L[k0 + i][tid] (bs3_load's update column, zero for
+// tid >= k0), so the block's Schur complement
+//     C_ij = R[k0+i][k0+j] - sum_{t < k0} l_i,t conj(l_j,t)      (i >= j)
+// is a workgroup reduction of ten products: DPP within the wave, the four wave sums through LDS,
+// added in wave order -- a fixed order, no atomics.  Wave 0 then factors C under factor_diag_lds's
+// pivot rules (a pivot not above a.tol[b] is flagged and dropped, clamped under kSolveClampHpd),
+// applies D^-1 to the block's y rows and publishes zcur / dcur as bs3_step reads them: L_cc on
+// the diagonal, conj(D^-1) above it.  Nothing reads the factored block after the solve, so R keeps
+// the raw one.  scr: 60 entries of LDS no one else uses before the caller's barrier.
+template <int NR>
+__device__ __forceinline__ void tail_fold(const MstepArgs& a, const cd* R, const cd* yg, int L, int b,
+                                          int k0, int tid, int lane, int wave, Bs3Buf& bf, cd* zcur,
+                                          cd* dcur, cd* scr) {
+    constexpr int W = 4;                                     // widest folded remainder
+    const int w = L - k0;
+    cd l4[W];
+#pragma unroll
+    for (int cc = 0; cc < W; ++cc)
+        l4[cc] = (tid < k0 && cc < w) ? R[(size_t)(k0 + cc) * L + tid] : czero();
+    if (tid < W * W) {                                       // the raw block's lower part
+        const int i = tid >> 2, j = tid & 3;
+        scr[40 + tid] = (i < w && j <= i) ? R[(size_t)(k0 + i) * L + k0 + j] : czero();
+    }
+    if (tid < w * NR) zcur[tid] = yg[(size_t)k0 * NR + tid];   // the raw y rows
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            if (i < w) {                                     // wave-uniform
+                const cd p = cmulc(l4[i], l4[j]);
+                const double sx = wave_sum_dpp(p.x), sy = wave_sum_dpp(p.y);
+                if (lane == 0) scr[wave * 10 + i * (i + 1) / 2 + j] = cmk(sx, sy);
+            }
+        }
+    __syncthreads();
+    // every thread clears its entry of the diagonal block but the 4 x 4 corner, which lane 0 writes
+    if (!((tid >> 4) < W && (tid & 15) < W)) dcur[tid] = czero();
+    if (wave == 0) {
+        cd A[W][W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                const int e = i * (i + 1) / 2 + j;
+                A[i][j] = czero();
+                if (i < w) {
+                    const cd s0 = scr[e], s1 = scr[10 + e], s2 = scr[20 + e], s3 = scr[30 + e];
+                    A[i][j] = csub(scr[40 + 4 * i + j], cmk(((s0.x + s1.x) + s2.x) + s3.x,
+                                                             ((s0.y + s1.y) + s2.y) + s3.y));
+                }
+            }
+        }
+        const double tol = a.tol[b];
+        double dinv[W];
+        bool bad_any = false;
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+            dinv[c] = 0.0;
+            if (c < w) {
+                const double dia = A[c][c].x;
+                const bool bad = !(dia > tol);
+                bad_any |= bad;
+                const bool drop = bad && a.solve_mode != kSolveClampHpd;
+                const double pv = bad ? tol : dia;
+                const double rs = fast_rsqrt64(pv);
+                const double inv = drop ? 0.0 : rs;
+                // the trailing update from the unscaled column, as factor_diag_lds does it
+#pragma unroll
+                for (int c2 = c + 1; c2 < W; ++c2) {
+                    const cd lcs = cscale(cconj(A[c2][c]), inv * inv);
+#pragma unroll
+                    for (int r = c2; r < W; ++r) A[r][c2] = csub(A[r][c2], cmul(A[r][c], lcs));
+                }
+#pragma unroll
+                for (int r = c + 1; r < W; ++r) A[r][c] = cscale(A[r][c], inv);
+                A[c][c] = cmk(drop ? 0.0 : pv * rs, 0.0);
+                dinv[c] = inv;
+            }
+        }
+        // Di = D^-1 (lower) by rows; a dropped direction (dinv = 0) zeroes its row and column
+        cd Di[W][W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+#pragma unroll
+            for (int j = 0; j < i; ++j) {
+                cd acc = czero();
+#pragma unroll
+                for (int k = j; k < i; ++k) acc = cfma(acc, A[i][k], Di[k][j]);
+                Di[i][j] = cscale(acc, -dinv[i]);
+            }
+            Di[i][i] = cmk(dinv[i], 0.0);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+#pragma unroll
+                for (int j = 0; j < W; ++j)
+                    dcur[i * NB + j] = j < i ? czero() : (j == i ? A[i][i] : cconj(Di[j][i]));
+                scr[56 + i] = cmk(dinv[i], 0.0);
+            }
+            if (bad_any && a.status) atomicOr(&a.status[b], a.clamp_status);
+        }
+        wave_sync();
+        // z = D^-1 y, one entry per lane (D^-1's row from what lane 0 just published)
+        const int i = lane / NR, q = lane - (lane / NR) * NR;
+        cd z = czero();
+        if (lane < w * NR) {
+            for (int j = 0; j < i; ++j) z = cfma(z, cconj(dcur[j * NB + i]), zcur[j * NR + q]);
+            z = cfma(z, scr[56 + i], zcur[i * NR + q]);
+        }
+        wave_sync();                                         // every raw y row is read
+        if (lane < w * NR) zcur[lane] = z;
+    }
+    bf.dd = czero();
+#pragma unroll
+    for (int cc = 0; cc < W; ++cc) bf.lv[cc] = l4[cc];
+#pragma unroll
+    for (int cc = W; cc < NB; ++cc) bf.lv[cc] = czero();
+}
+
 // The same one-barrier block step with the factor entries loaded ONE step ahead into a single
 // buffer (issued as soon as the update has consumed the current one, the next diagonal-block
 // entry at the start of the step): ~100 VGPRs instead of backsub3's 192, so four trials'
 // workgroups are resident per CU (one round over ~1000 trials instead of two).
-template <int NR>
+//
+// FOLD (the remainder fold): the last panel, w <= 4 columns wide, had no update
+// and no factor launch of its own -- its rows of L (columns < k0) and its y rows are final (every
+// earlier factor launch carried them as its last row tile), its diagonal block is still R's.  The
+// head of this kernel factors it (tail_fold) and publishes the block as a factor launch would have.
+template <int NR, bool FOLD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 void backsub4_kernel(MstepArgs a, int L) {
     __shared__ cd zb[2][NB * NR];              // the current / next block's z rows
@@ -1491,8 +1617,12 @@ void backsub4_kernel(MstepArgs a, int L) {
 #pragma unroll
     for (int q = 0; q < NR; ++q) yr[q] = tid < L ? yg[(size_t)tid * NR + q] : czero();
     Bs3Buf bf;
-    bs3_load(R, L, nblk - 1, tid, bf);
-    {
+    if constexpr (FOLD) {
+        // the buffers of block nblk - 2 are free until the first block step's end: the scratch
+        tail_fold<NR>(a, R, yg, L, b, (nblk - 1) * NB, tid, lane, wave, bf, zb[(nblk - 1) & 1],
+                      db[(nblk - 1) & 1], db[nblk & 1]);
+    } else {
+        bs3_load(R, L, nblk - 1, tid, bf);
         // the last block's rows (k0 may be 256: no owner thread) straight from the input
         const int k0 = (nblk - 1) * NB, w = L - k0;
         if (tid < w * NR) zb[(nblk - 1) & 1][tid] = yg[(size_t)k0 * NR + tid];
@@ -1560,17 +1690,25 @@ hipError_t launch_chol_batched(const Problem& pb, const MstepArgs& a, hipStream_
     hipError_t e = launch_diag_tol(pb, a, s);
     if (e != hipSuccess) return e;
     const int npan = (pb.L + PW - 1) / PW;
+    // default back substitution (L <= 272, NR <= 4): the one-buffer one-barrier kernel; otherwise,
+    // or with SBCE_BACKSUB=1 (cross-check), the general kernel
+    const bool bs4 = pb.L <= 272 && pb.NR <= 4 && !g_debug.backsub_general && !(skip & 16);
+    // the remainder fold: a last panel of at most 4 columns gets no update and no factor launch,
+    // backsub4_kernel<NR, true> factors it at its head (every diagnostic mask keeps the old schedule)
+    const int wlast = pb.L - PW * (npan - 1);
+    const bool fold = bs4 && npan >= 2 && wlast <= 4 && skip == 0;
+    const int nfac = fold ? npan - 1 : npan;
     // the wide schedule: even panels j >= 2 update panels j and j+1 by [0, jb) in one launch
     // (panel_update2_kernel), odd panels are pre-updated by panel j-1 inside their factor launch:
     // half the left-looking HBM re-reads of one update launch per panel
     const bool g3 = g_debug.cplx3 && (a.solve_mode == SBCE_SOLVE_CHOL || a.solve_mode == kSolveClampHpd);
-    for (int j = 0; j < npan; ++j) {
+    for (int j = 0; j < nfac; ++j) {
         const int jb = j * PW;
         const int rem = (pb.L - jb + NB - 1) / NB;
         if (j >= 2 && !(j & 1)) {
             ct_begin(s, 0);
             const int gpt0 = (rem + 3) / 4;
-            const int gpt1 = j + 1 < npan ? (rem - 2 + 3) / 4 : 0;
+            const int gpt1 = j + 1 < nfac ? (rem - 2 + 3) / 4 : 0;
             const long nblk = 8L * ((pb.B + 7) / 8) * (gpt0 + gpt1);
             if (g3)
                 hipLaunchKernelGGL(panel_update2_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, s, a, pb.L,
@@ -1603,15 +1741,14 @@ hipError_t launch_chol_batched(const Problem& pb, const MstepArgs& a, hipStream_
         ct_end(s);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    // default (L <= 272, NR <= 4): the one-buffer one-barrier kernel; otherwise, or with
-    // SBCE_BACKSUB=1 (cross-check), the general kernel
-    if (pb.L <= 272 && pb.NR <= 4 && !g_debug.backsub_general && !(skip & 16)) {
+    if (bs4) {
         ct_begin(s, 2);
-        switch (pb.NR) {
-            case 1: hipLaunchKernelGGL(backsub4_kernel<1>, dim3(pb.B), dim3(256), 0, s, a, pb.L); break;
-            case 2: hipLaunchKernelGGL(backsub4_kernel<2>, dim3(pb.B), dim3(256), 0, s, a, pb.L); break;
-            case 3: hipLaunchKernelGGL(backsub4_kernel<3>, dim3(pb.B), dim3(256), 0, s, a, pb.L); break;
-            default: hipLaunchKernelGGL(backsub4_kernel<4>, dim3(pb.B), dim3(256), 0, s, a, pb.L); break;
+        switch (pb.NR * 2 + (fold ? 1 : 0)) {
+#define SBCE_BS4(nr) \
+    case 2 * nr: hipLaunchKernelGGL((backsub4_kernel<nr, false>), dim3(pb.B), dim3(256), 0, s, a, pb.L); break; \
+    case 2 * nr + 1: hipLaunchKernelGGL((backsub4_kernel<nr, true>), dim3(pb.B), dim3(256), 0, s, a, pb.L); break;
+            SBCE_BS4(1) SBCE_BS4(2) SBCE_BS4(3) SBCE_BS4(4)
+#undef SBCE_BS4
         }
         ct_end(s);
         return hipGetLastError();
