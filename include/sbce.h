@@ -187,7 +187,14 @@ int sbce_workspace_bytes_solve(const sbce_dims* d, int solve_mode, size_t* bytes
 
 /* Full EM: `iters` iterations of E-step + M-step on every trial of the batch.
  * Replaces em() at Proposed_method_NMSEvsTp.py:50-83 (estep_mode SOFT) and the
- * hard-ML em() at ML_detecctor.py:51-86 (estep_mode HARD, llf != NULL). */
+ * hard-ML em() at ML_detecctor.py:51-86 (estep_mode HARD, llf != NULL).
+ * The chain is a deterministic function of theta per trial, so once an M-step returns the theta
+ * it was given bit for bit, the trial's later iterations are not executed: they would reproduce
+ * it.  theta, status, x_dest and iters_done (= iters) are those of the full chain, bit for bit;
+ * only the time differs (high-SNR soft EM and hard-decision EM typically settle within a few
+ * iterations).  This applies to the batched Cholesky solve (n_tx in {4, 8} or L > 64, L <= 512,
+ * not SBCE_SOLVE_MINNORM) without h_true, llf and x_sup; every other call executes all
+ * iterations, as do sbce_em_noise and sbce_em_conv (whose own rule stops trials). */
 int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode,
             int solve_mode, void* hip_stream);
 

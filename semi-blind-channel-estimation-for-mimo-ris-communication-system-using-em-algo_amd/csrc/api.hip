@@ -393,8 +393,18 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
                                     small2 ? list_cnt : nullptr, s))))
         return rc;
 
+    // The fixed-point freeze: the plain chain is a pure function of theta per
+    // trial, so once the back substitution stores the theta it overwrites bit for bit, the trial's
+    // later iterations would repeat this one -- the back substitution flags the trial and the
+    // kernels skip it.  Armed only where theta is the whole state and nothing reads it per
+    // iteration: not with the noise estimate, the conv stop (it owns the flags), the oracle stop
+    // (iters_done counts executed iterations), the LLF history or superimposed pilots, and only
+    // on the batched-panel solve, whose back substitutions carry the fold.
+    const bool freeze = !nz && !cv && !early && !p->llf && !p->x_sup && !small &&
+                        chol_batched_selected(pb, solve_mode);
+
     EstepArgs ea = estep_args(p, ws + c.mom, ws, &c);
-    ea.done = (early || cv) ? done : nullptr;
+    ea.done = (early || cv || freeze) ? done : nullptr;
     if (nz) {                                // the estimate starts at the caller's parameter
         if ((rc = hip_rc(launch_noise_init(pb.B, nz->varn_est, p->varn_t, pb.varn, s)))) return rc;
         ea.varn_t = nz->varn_est;
@@ -402,6 +412,7 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
     ea.lists_zeroed = small2 && list_cnt != nullptr;
     MstepArgs ma = mstep_args(pb, p, ea.mom, ws, c, solve_mode);
     ma.done = ea.done;
+    if (freeze) ma.freeze_w = done;
 
     EstepArgs eas = ea;                      // superimposed pilots: E-step on y - H x_p
     if (p->x_sup) eas.yd = (const cd*)(ws + c.ysh);

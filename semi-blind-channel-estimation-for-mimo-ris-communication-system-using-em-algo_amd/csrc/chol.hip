@@ -1394,6 +1394,16 @@ void panel_factor_kernel(MstepArgs a, int L, int NR, int jb, int ntile, int skip
 }
 
 // ---------------------------------------------------------------- back substitution
+// Fixed-point detection: nonzero when the two values differ in any bit -- an
+// integer compare, so +0 and -0 differ and a NaN equals itself.
+__device__ __forceinline__ unsigned theta_bits_differ(const cd& u, const cd& v) {
+    const unsigned long long d = ((unsigned long long)__double_as_longlong(u.x) ^
+                                  (unsigned long long)__double_as_longlong(v.x)) |
+                                 ((unsigned long long)__double_as_longlong(u.y) ^
+                                  (unsigned long long)__double_as_longlong(v.y));
+    return (unsigned)(d | (d >> 32));
+}
+
 // General blocked back substitution L^H x = y (any L <= 512, any NR; SBCE_BACKSUB=1 forces it
 // for the shapes backsub4_kernel covers, as a cross-check), theta = conj(x).
 __global__ __launch_bounds__(256) void backsub_kernel(MstepArgs a, int L, int NR, int skip) {
@@ -1410,6 +1420,16 @@ __global__ __launch_bounds__(256) void backsub_kernel(MstepArgs a, int L, int NR
     back_substitute_pf<2>(R, y, L, NR, tid, nth, lane, wave, (skip & 16) ? (L + NB - 1) / NB : 0, L,
                           y + L * NR);
     cd* th = a.theta + (size_t)b * L * NR;
+    if (a.freeze_w) {                                        // the fixed-point fold (backsub4_kernel)
+        unsigned diff = 0;
+        for (int e = tid; e < L * NR; e += nth) {
+            const cd old = th[e], x = cconj(y[e]);
+            diff |= theta_bits_differ(old, x);
+            th[e] = x;
+        }
+        if (!__syncthreads_or(diff != 0) && tid == 0) a.freeze_w[b] = 1;
+        return;
+    }
     for (int e = tid; e < L * NR; e += nth) th[e] = cconj(y[e]);
 }
 
@@ -1629,10 +1649,18 @@ void backsub4_kernel(MstepArgs a, int L) {
         db[(nblk - 1) & 1][tid] = bf.dd;
     }
     __syncthreads();
+    // Fixed-point fold (armed by a.freeze_w): the storing lane loads the entry of theta it is about
+    // to overwrite -- this iteration's E-step input -- at the head of the block step and compares
+    // the bit patterns after the step's wave_sync; the OR is carried through the block steps.
+    const bool arm = a.freeze_w != nullptr;
+    unsigned diff = 0;
     for (int kb = nblk - 1; kb >= 0; --kb) {
         const int k0 = kb * NB, w = (L - k0) < NB ? (L - k0) : NB;
         cd dnext = czero();                    // entry of the next diagonal block (k0 - 16 ..)
         if (kb > 0 && dc2 >= dc) dnext = R[(size_t)(k0 - NB + dc) * L + k0 - NB + dc2];
+        const bool cmp = arm && wave == 0 && c < w;
+        cd told = czero();
+        if (cmp) told = th[(size_t)(k0 + c) * NR + r];
         const cd* z = zb[kb & 1];
         const cd* d = db[kb & 1] + c * NB;     // row c: L_cc, then conj(Di[c2][c]) for c2 > c
         cd x = czero();
@@ -1644,6 +1672,7 @@ void backsub4_kernel(MstepArgs a, int L) {
         if (lane < NB * NR) xw[wave][lane] = x;
         if (wave == 0 && c < w) th[(size_t)(k0 + c) * NR + r] = cconj(x);
         wave_sync();
+        if (cmp) diff |= theta_bits_differ(told, cconj(x));
         if (tid < k0) {
 #pragma unroll
             for (int cc = 0; cc < NB; ++cc)
@@ -1667,6 +1696,8 @@ void backsub4_kernel(MstepArgs a, int L) {
         }
         __syncthreads();
     }
+    // no entry of theta changed a bit: every later iteration of this trial would repeat this one
+    if (arm && wave == 0 && __ballot(diff != 0) == 0 && lane == 0) a.freeze_w[b] = 1;
 }
 
 // DIAGNOSTIC launch timing (sbce_debug_chol_timing): HIP events around the wide schedule's
@@ -1838,6 +1869,12 @@ hipError_t launch_chol_tile(const Problem& pb, const MstepArgs& a, int k0, int w
     hipLaunchKernelGGL((chol_mfma_kernel<1, false, 4, 128, false>), dim3(pb.B), dim3(64 * ntile),
                        lds, s, a, w, pb.NR, 0, geo);
     return hipGetLastError();
+}
+
+// launch_chol_solve takes the batched-panel path, which ends in backsub4_kernel or backsub_kernel
+// (the two back substitutions that carry the fixed-point fold)
+bool chol_batched_selected(const Problem& pb, int solve_mode) {
+    return solve_mode != SBCE_SOLVE_MINNORM && pb.L <= kLargeL && !g_debug.chol_valu;
 }
 
 hipError_t launch_chol_solve(const Problem& pb, const MstepArgs& a, hipStream_t s) {

@@ -354,6 +354,7 @@ __global__ __launch_bounds__(256) void rbuild_herm_kernel(MstepArgs a, int B, in
 // tol[b] = 1e-14 max_i Re R[i][i] of the freshly built R (chol.hip's pivot threshold).
 __global__ __launch_bounds__(256) void diag_tol_kernel(MstepArgs a, int L) {
     const int b = blockIdx.x;
+    if (a.done && a.done[b]) return;
     const cd* R = a.R + (size_t)b * L * L;
     __shared__ double red[4];
     double m = 0.0;

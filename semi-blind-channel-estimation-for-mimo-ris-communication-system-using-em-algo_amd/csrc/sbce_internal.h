@@ -411,6 +411,9 @@ struct MstepArgs {
     int32_t* iters_done = nullptr;
     int it = 0;
     int32_t* zero_cnt = nullptr;  // the small solve launch zeroes these 5 E-step list counters
+    // the fixed-point freeze folded into the back substitution of the batched-panel solve: set to 1
+    // when the stored theta equals the one it overwrites bit for bit (null: not armed)
+    int32_t* freeze_w = nullptr;  // [B]
 };
 
 // Per-trial extents of one tiled-factorisation launch sequence (mstep_large.hip): column
@@ -432,6 +435,8 @@ int estep_prep_stride(const Problem& pb);   // doubles per symbol, 0 if no MFMA 
 hipError_t launch_mstep_build(const Problem& pb, const MstepArgs& a, hipStream_t s,
                               bool pilots_factored = false);
 hipError_t launch_chol_solve(const Problem& pb, const MstepArgs& a, hipStream_t s);
+// launch_chol_solve takes the batched-panel path (its back substitutions honour MstepArgs::freeze_w)
+bool chol_batched_selected(const Problem& pb, int solve_mode);
 bool chol_supported(const Problem& pb);
 // L <= 64 (n_tx not 4, 8), CHOL / CHOL_DROP: build + solve of one trial in one workgroup
 // (mstep_small.hip); write_sys also stores R and B^H in a.R / a.rhs (sbce_mstep's outputs)
