@@ -75,7 +75,7 @@ constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
 struct Carve {
-    size_t mom, R, rhs, done, ysh, prep, list, tree, tol, winv, ppsi, pS, pflag, prhs, gram, grhs,
+    size_t mom, R, rhs, done, mchg, ysh, prep, list, tree, tol, winv, ppsi, pS, pflag, prhs, gram, grhs,
         act, tol2, dvec, mnr, mnskip, total;
     bool has_prep, has_prhs, has_winv, has_mn;
 };
@@ -108,6 +108,9 @@ Carve carve(const Problem& pb, int solve = kAnySolve) {
     c.rhs = align_up(c.R + (size_t)pb.B * pb.L * pb.L * sizeof(cd));
     c.done = align_up(c.rhs + (size_t)pb.B * pb.L * pb.NR * sizeof(cd));
     c.ysh = align_up(c.done + (size_t)pb.B * sizeof(int32_t));         // superimposed pilots
+    // the moment-repeat words [B] int32 (em_run) share the head of the shifted observations: the
+    // rule is never armed with superimposed pilots, and the region holds >= 16 bytes per trial
+    c.mchg = c.ysh;
     c.prep = align_up(c.ysh + (size_t)pb.B * pb.Td * pb.NR * sizeof(cd));   // MFMA sweep prep
     const int ps = estep_prep_stride(pb);
     c.has_prep = ps > 0;
@@ -389,9 +392,6 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
     // iteration, em_init_kernel for the first -- no counter memset per E-step
     const bool small2 = small && mstep_small2_selected(pb);
     int32_t* list_cnt = c.has_prep ? (int32_t*)(ws + c.list) + (size_t)pb.B * pb.Td : nullptr;
-    if ((rc = hip_rc(launch_em_init(pb.B, done, p->status, debug_nondefault() ? SBCE_STATUS_DEBUG : 0,
-                                    small2 ? list_cnt : nullptr, s))))
-        return rc;
 
     // The fixed-point freeze: the plain chain is a pure function of theta per
     // trial, so once the back substitution stores the theta it overwrites bit for bit, the trial's
@@ -402,6 +402,18 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
     // on the batched-panel solve, whose back substitutions carry the fold.
     const bool freeze = !nz && !cv && !early && !p->llf && !p->x_sup && !small &&
                         chol_batched_selected(pb, solve_mode);
+    // The moment-repeat rule: the M-step is a pure function of the moments and
+    // the call's constant inputs, so a trial whose E-step rewrote its moments bit for bit is at
+    // its fixed point one M-step before the theta compare sees it.  The moment stores of the
+    // E-step flag a change in mchg[b]; the M-step's launches skip a trial without one and the
+    // back substitution freezes it.  Armed with the freeze, and only where every moment writer of
+    // the launched E-step carries the fold.
+    const bool momfreeze = freeze && estep_momfold_supported(pb, estep_mode);
+    int32_t* mchg = momfreeze ? (int32_t*)(ws + c.mchg) : nullptr;
+    if ((rc = hip_rc(launch_em_init(pb.B, done, mchg, p->status,
+                                    debug_nondefault() ? SBCE_STATUS_DEBUG : 0,
+                                    small2 ? list_cnt : nullptr, s))))
+        return rc;
 
     EstepArgs ea = estep_args(p, ws + c.mom, ws, &c);
     ea.done = (early || cv || freeze) ? done : nullptr;
@@ -413,6 +425,7 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
     MstepArgs ma = mstep_args(pb, p, ea.mom, ws, c, solve_mode);
     ma.done = ea.done;
     if (freeze) ma.freeze_w = done;
+    if (momfreeze) ma.mchg = mchg;
 
     EstepArgs eas = ea;                      // superimposed pilots: E-step on y - H x_p
     if (p->x_sup) eas.yd = (const cd*)(ws + c.ysh);
@@ -448,6 +461,8 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
             if ((rc = hip_rc(launch_sup_shift_mom(pb, ea.mom, (const cd*)p->x_sup, ea.done, s))))
                 return rc;
         } else {
+            // iteration 0: mom holds stale contents -- nothing to compare with, every trial changed
+            ea.mchg = (momfreeze && it > 0) ? mchg : nullptr;
             if ((rc = hip_rc(launch_estep(pb, ea, estep_mode, s)))) return rc;
         }
         if (small) {
@@ -461,6 +476,7 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
             }
             if ((rc = hip_rc(launch_mstep_small(pb, ms, false, s)))) return rc;
         } else {
+            if (momfreeze && it > 0) ma.mskip = mchg;
             if ((rc = hip_rc(launch_mstep_build(pb, ma, s, prefactor)))) return rc;
             // Gaussian prior, n_rx = 1: the reference's all-ones covariance term stays in A
             // (MIMO_Gaussian_proposed.py:73-76): R += c 1 1^T
@@ -726,6 +742,19 @@ int sbce_debug_reload_env(void) {
 int sbce_debug_estep_mfma(unsigned long long* out, int reset) {
     if (!reset && !out) return SBCE_EINVAL;
     return hip_rc(estep_debug_mfma(out, reset));
+}
+
+// Diagnostic, not part of include/sbce.h: trial-M-steps the moment-repeat rule of sbce_em skipped
+// since the last reset (every stream); reset != 0 clears the counter.  The counter exists only in
+// the A/B build: the product library returns SBCE_EUNSUPPORTED.
+int sbce_debug_momskip(unsigned long long* out, int reset) {
+#if SBCE_AB
+    if (!reset && !out) return SBCE_EINVAL;
+    return hip_rc(mstep_debug_momskip(out, reset));
+#else
+    (void)out; (void)reset;
+    return SBCE_EUNSUPPORTED;
+#endif
 }
 
 // Diagnostic, not part of include/sbce.h: symbols the sphere pass resolved by enumeration

@@ -871,7 +871,7 @@ __global__ __launch_bounds__(256) void panel_update2_kernel(MstepArgs a, int L, 
     const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
     const int b = (slot / gpt) * 8 + xcd, g = slot - (slot / gpt) * gpt;
     if (b >= a.nbatch) return;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     if (g < gpt0) panel_update_body<4, G3>(a, L, jb, jb, ntile, b, g, skip, Bp);
     else panel_update_body<4, G3>(a, L, jb + PW, jb, ntile - 2, b, g - gpt0, skip, Bp);
 }
@@ -1388,12 +1388,31 @@ void panel_factor_kernel(MstepArgs a, int L, int NR, int jb, int ntile, int skip
     __shared__ int ctl[4];
     __shared__ int defl[kFacMaxTile];
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const unsigned long long t0 = CLK ? __builtin_amdgcn_s_memtime() : 0;   // diagnostic
     panel_factor_body<G3, PRE, CLK>(a, L, NR, jb, ntile, b, skip, sm, dinv, ctl, defl, t0);
 }
 
 // ---------------------------------------------------------------- back substitution
+// Moment-repeat rule, at the head of the back substitution -- the M-step's last
+// launch, one workgroup per trial: a live trial whose E-step rewrote its moments bit for bit
+// (mstep_skip: every earlier launch of this M-step skipped it) is at its fixed point; the trial is
+// flagged as the theta compare would have flagged it after the M-step.  Block-uniform.
+#if SBCE_AB
+__device__ unsigned long long g_mom_skip;      // trial-M-steps skipped (sbce_debug_momskip)
+#endif
+__device__ __forceinline__ bool backsub_skip(const MstepArgs& a, int b, int tid) {
+    if (a.done && a.done[b]) return true;
+    if (!(a.mskip && !a.mskip[b])) return false;
+    if (tid == 0) {
+        a.freeze_w[b] = 1;
+#if SBCE_AB
+        atomicAdd(&g_mom_skip, 1ull);
+#endif
+    }
+    return true;
+}
+
 // Fixed-point detection: nonzero when the two values differ in any bit -- an
 // integer compare, so +0 and -0 differ and a NaN equals itself.
 __device__ __forceinline__ unsigned theta_bits_differ(const cd& u, const cd& v) {
@@ -1410,13 +1429,15 @@ __global__ __launch_bounds__(256) void backsub_kernel(MstepArgs a, int L, int NR
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cd* y = reinterpret_cast<cd*>(smem);
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
     const int tid = threadIdx.x, lane = tid & 63, nth = blockDim.x;     // 2 nth >= L
+    if (backsub_skip(a, b, tid)) return;
     const int wave = tid >> 6;
     const cd* R = a.R + (size_t)b * L * L;
     const cd* yg = a.rhs + (size_t)b * L * NR;
     for (int e = tid; e < L * NR; e += nth) y[e] = yg[e];
     __syncthreads();
+    // every thread has read the trial's word: cleared for the next E-step
+    if (a.mchg && tid == 0) a.mchg[b] = 0;
     back_substitute_pf<2>(R, y, L, NR, tid, nth, lane, wave, (skip & 16) ? (L + NB - 1) / NB : 0, L,
                           y + L * NR);
     cd* th = a.theta + (size_t)b * L * NR;
@@ -1624,8 +1645,8 @@ void backsub4_kernel(MstepArgs a, int L) {
     __shared__ cd db[2][NB * NB];              // the current / next diagonal block
     __shared__ cd xw[4][NB * NR];              // per-wave block solution
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
     const int tid = threadIdx.x, lane = tid & 63;
+    if (backsub_skip(a, b, tid)) return;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const cd* R = a.R + (size_t)b * L * L;
     const cd* yg = a.rhs + (size_t)b * L * NR;
@@ -1649,6 +1670,8 @@ void backsub4_kernel(MstepArgs a, int L) {
         db[(nblk - 1) & 1][tid] = bf.dd;
     }
     __syncthreads();
+    // every thread has read the trial's word of the moment-repeat rule: cleared for the next E-step
+    if (a.mchg && tid == 0) a.mchg[b] = 0;
     // Fixed-point fold (armed by a.freeze_w): the storing lane loads the entry of theta it is about
     // to overwrite -- this iteration's E-step input -- at the head of the block step and compares
     // the bit patterns after the step's wave_sync; the OR is carried through the block steps.
@@ -1835,6 +1858,18 @@ hipError_t chol_debug_timing(int mode, double* out6) {
         out6[3 + k] += 1.0;
     }
     return hipSuccess;
+}
+
+hipError_t mstep_debug_momskip(unsigned long long* out, int reset) {
+#if SBCE_AB
+    if (reset) {
+        const unsigned long long z = 0;
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_mom_skip), &z, sizeof(z), 0, hipMemcpyHostToDevice);
+    }
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mom_skip), sizeof(*out), 0, hipMemcpyDeviceToHost);
+#else
+    return hipErrorNotSupported;
+#endif
 }
 
 hipError_t chol_debug_clock(unsigned long long* out) {

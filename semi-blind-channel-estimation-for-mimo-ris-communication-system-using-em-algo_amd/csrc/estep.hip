@@ -1270,18 +1270,21 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     if (c.count && lane == 0) atomicAdd(&g_estep_mfma, (unsigned long long)groups * STEPS * TU);
     constexpr int MS = NT + NT * NT;
     cd* out = a.mom + (size_t)gsym * MS;
+    // The moment-repeat fold (armed by a.mchg): the lane that stores output word `lane` loads the
+    // word it overwrites ahead of the reduction and compares the bit patterns at the store.
+    const bool arm = a.mchg != nullptr;
+    cd mold = czero();
+    if (arm && lane < MS) mold = out[lane];
     if (MODE == SBCE_ESTEP_HARD) {
         wave_argmin_dpp(best_d, best_j);
-        if (lane == 0) {
-            cd x[NT];
-#pragma unroll
-            for (int s2 = 0; s2 < NT; ++s2) x[s2] = s_cons[(best_j >> (k_lm * (NT - 1 - s2))) & mask];
-#pragma unroll
-            for (int s2 = 0; s2 < NT; ++s2) {
-                out[s2] = x[s2];
-#pragma unroll
-                for (int s3 = 0; s3 < NT; ++s3) out[NT + s2 * NT + s3] = cmulc(x[s2], x[s3]);
-            }
+        if (lane < MS) {                       // lane o writes output o (m_t, then S_t row-major)
+            const int s2 = lane < NT ? lane : (lane - NT) / NT;
+            const int s3 = lane < NT ? 0 : (lane - NT) % NT;
+            const cd xp = s_cons[(best_j >> (k_lm * (NT - 1 - s2))) & mask];
+            const cd xq = s_cons[(best_j >> (k_lm * (NT - 1 - s3))) & mask];
+            const cd mv = lane < NT ? xp : cmulc(xp, xq);
+            out[lane] = mv;
+            if (arm && mom_bits_differ(mold, mv)) a.mchg[b] = 1;
         }
         return;
     }
@@ -1356,7 +1359,9 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
             }
             const double iz = 1.0 / red[0];
             const double re = red[ire], im = iim >= 0 ? red[iim] : 0.0;
-            out[lane] = cmk(re * iz, (cj ? -im : im) * iz);
+            const cd mv = cmk(re * iz, (cj ? -im : im) * iz);
+            out[lane] = mv;
+            if (arm && mom_bits_differ(mold, mv)) a.mchg[b] = 1;
         }
     }
     }();
@@ -2005,12 +2010,16 @@ __global__ __launch_bounds__(256) void estep_tree_kernel(EstepArgs a, PrepConst 
                 xo[q] = v;
             }
             cd* mo = a.mom + (size_t)gsym * MS;
+            const bool arm = a.mchg != nullptr;          // the moment-repeat fold
+            unsigned chg = 0;
 #pragma unroll
             for (int p2 = 0; p2 < NT; ++p2) {
-                mo[p2] = xo[p2];
+                mom_store(mo + p2, xo[p2], arm, chg);
 #pragma unroll
-                for (int q = 0; q < NT; ++q) mo[NT + p2 * NT + q] = cmulc(xo[p2], xo[q]);
+                for (int q = 0; q < NT; ++q)
+                    mom_store(mo + NT + p2 * NT + q, cmulc(xo[p2], xo[q]), arm, chg);
             }
+            if (chg) a.mchg[gsym / c.Td] = 1;            // (b is not kept live this far)
         }
     }
     // the tree record: only the enumeration reads it (not the single-path symbols, nor the
@@ -2222,7 +2231,9 @@ __global__ __launch_bounds__(64 * kBfsWaves) void estep_bfs_kernel(EstepArgs a, 
                     const int q = lane < NT ? 0 : (lane - NT) % NT;
                     const cd xp = s_cons[(bj >> (lm * (NT - 1 - p2))) & mask];
                     const cd xq = s_cons[(bj >> (lm * (NT - 1 - q))) & mask];
-                    mo[lane] = lane < NT ? xp : cmulc(xp, xq);
+                    unsigned chg = 0;                  // the moment-repeat fold
+                    mom_store(mo + lane, lane < NT ? xp : cmulc(xp, xq), a.mchg != nullptr, chg);
+                    if (chg) a.mchg[gsym / c.Td] = 1;
                 }
             } else {
                 // the n_in leaves inside the sphere (LDS list, level order): lane o < MS forms
@@ -2253,6 +2264,11 @@ __global__ __launch_bounds__(64 * kBfsWaves) void estep_bfs_kernel(EstepArgs a, 
                         lp = st == sp_ ? l : lp;
                         lq = st == sq_ ? l : lq;
                     }
+                    // the moment-repeat fold: the word this lane overwrites, loaded ahead of the
+                    // leaf loop
+                    const bool arm = a.mchg != nullptr;
+                    cd mold = czero();
+                    if (arm) mold = mo[lane];
                     double z = 0.0;
                     cd v = czero();
                     for (int k = 0; k < n_in; ++k) {
@@ -2265,7 +2281,9 @@ __global__ __launch_bounds__(64 * kBfsWaves) void estep_bfs_kernel(EstepArgs a, 
                             v = caxpy(v, w, lane < NT ? xp : cmulc(xp, xq));
                         }
                     }
-                    mo[lane] = cscale(v, 1.0 / z);
+                    const cd mv = cscale(v, 1.0 / z);
+                    mo[lane] = mv;
+                    if (arm && mom_bits_differ(mold, mv)) a.mchg[gsym / c.Td] = 1;
                 }
             }
         }
@@ -2492,6 +2510,18 @@ bool estep_supported(const Problem& pb, int mode) {
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return estep_pm_supported(pb, pb.pr, mode);
     Geometry g;
     return (mode == SBCE_ESTEP_SOFT || mode == SBCE_ESTEP_HARD) && make_geometry(pb, g);
+}
+
+// The moment writers of launch_estep that fold EstepArgs::mchg: the tree pass's single-path store,
+// the enumeration, the n_tx = 4 factorised-weight pass and the MFMA sweep (listed or not) -- every
+// writer of a soft / hard E-step that takes the sweep branch below at n_tx >= 3.  Not the VALU
+// kernel, the n_tx = 2 factorised passes (estep_pair.hip) or the PM / ZF / MMSE / Gauss kernels.
+bool estep_momfold_supported(const Problem& pb, int mode) {
+    if (mode != SBCE_ESTEP_SOFT && mode != SBCE_ESTEP_HARD) return false;
+    MfmaConst mc;
+    size_t mlds;
+    long mblocks;
+    return !g_debug.estep_valu && pb.NT >= 3 && make_mfma(pb, mc, mlds, mblocks);
 }
 
 hipError_t launch_estep(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s) {

@@ -295,6 +295,10 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
         if (!(lane & 1)) red[jv] = vv[0];
         wave_sync();
         if (lane < NT + NT * NT) {
+            // the moment-repeat fold (armed by a.mchg): the storing lane loads the word it
+            // overwrites and compares the bit patterns at the store
+            cd* mout = a.mom + (size_t)gsym * (NT + NT * NT) + lane;
+            unsigned chg = 0;
             // m_a at 1 + 2a; E|x_a|^2 at 9 + a; E[x_a conj(x_b)], a < b, at 13, 15, 17 (0,1..3),
             // 19, 21 (1,2..3), 23 (2,3)
             int ire, iim = -1;
@@ -316,7 +320,8 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
             }
             const double iz = 1.0 / red[0];
             const double re = red[ire], im = iim >= 0 ? red[iim] : 0.0;
-            a.mom[(size_t)gsym * (NT + NT * NT) + lane] = cmk(re * iz, (cj ? -im : im) * iz);
+            mom_store(mout, cmk(re * iz, (cj ? -im : im) * iz), a.mchg != nullptr, chg);
+            if (chg) a.mchg[b] = 1;
         }
         if (c.count && lane == 0) atomicAdd(&g_estep_pair, 1ull);
     }

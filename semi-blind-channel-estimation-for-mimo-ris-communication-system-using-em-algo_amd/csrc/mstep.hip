@@ -25,7 +25,7 @@ template <int NT>
 __global__ __launch_bounds__(256) void rbuild_kernel(MstepArgs a, int B, int P, int Tp, int Td,
                                                      int L) {
     const int b = blockIdx.y;
-    if ((a.done && a.done[b]) || (a.gate && !a.gate[b])) return;
+    if (mstep_skip(a, b) || (a.gate && !a.gate[b])) return;
     const int npairs = P * (P + 1) / 2;
     const int pi = blockIdx.x * blockDim.x + threadIdx.x;
     if (pi >= npairs) return;
@@ -77,7 +77,7 @@ template <int NT>
 __global__ __launch_bounds__(256) void rbuild_wide_kernel(MstepArgs a, int B, int P, int Tp,
                                                           int Td, int L) {
     const int b = blockIdx.y;
-    if ((a.done && a.done[b]) || (a.gate && !a.gate[b])) return;
+    if (mstep_skip(a, b) || (a.gate && !a.gate[b])) return;
     const int npairs = P * (P + 1) / 2;
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     const int pi = gid / NT, i = gid - pi * NT;
@@ -119,7 +119,7 @@ template <int NR>
 __global__ __launch_bounds__(256) void rhs_kernel(MstepArgs a, int B, int P, int NT, int Tp,
                                                   int Td, int L) {
     const int b = blockIdx.y;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= L) return;
     const int p = l / NT, ai = l - p * NT;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(512) void rhs_lds_kernel(MstepArgs a, int P, int NT
     cd* s_m = s_ps + TCR * P;                        // [TCR][NT]
     cd* s_y = s_m + TCR * NT;                        // [TCR][NR]
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const int tid = threadIdx.x, nth = blockDim.x;
     const bool live = tid < L;
     const int l = live ? tid : L - 1;
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(512) void rhs_dma_kernel(MstepArgs a, int P, int NT
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int CH = TCR * (P + NT + NR);              // cd per chunk buffer: [TCR][P] [TCR][NT] [TCR][NR]
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nth >> 6;
     const bool live = tid < L;
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256) void gauss_rank1_kernel(MstepArgs a, int Td, i
                                                           int L) {
     __shared__ double sh[4];
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const int MS = NT + NT * NT;
     double c = 0.0;
     for (int t = threadIdx.x; t < Td; t += blockDim.x) {
@@ -622,20 +622,22 @@ hipError_t launch_llf(const Problem& pb, const cd* theta, const cd* yp, const cd
 }
 
 namespace {
-__global__ __launch_bounds__(256) void em_init_kernel(int B, int32_t* done, int32_t* status, int sv,
-                                                      int32_t* cnt) {
+__global__ __launch_bounds__(256) void em_init_kernel(int B, int32_t* done, int32_t* mchg, int32_t* status,
+                                                      int sv, int32_t* cnt) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < B) {
         done[i] = 0;
+        if (mchg) mchg[i] = 0;
         if (status) status[i] = sv;
     }
     if (cnt && i < 5) cnt[i] = 0;
 }
 }  // namespace
 
-hipError_t launch_em_init(int B, int32_t* done, int32_t* status, int sv, int32_t* cnt, hipStream_t s) {
+hipError_t launch_em_init(int B, int32_t* done, int32_t* mchg, int32_t* status, int sv, int32_t* cnt,
+                          hipStream_t s) {
     hipLaunchKernelGGL(em_init_kernel, dim3((B + 255) / 256 > 0 ? (B + 255) / 256 : 1), dim3(256), 0,
-                       s, B, done, status, sv, cnt);
+                       s, B, done, mchg, status, sv, cnt);
     return hipGetLastError();
 }
 

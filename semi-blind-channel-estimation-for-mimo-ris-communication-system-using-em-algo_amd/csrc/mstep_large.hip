@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void rbuild_herm_kernel(MstepArgs a, int B, in
     const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
     const int b = (slot / G) * 8 + xcd, g = slot - (slot / G) * G;
     if (b >= B) return;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const int npairs = P * (P + 1) / 2;
     const int pi0 = g * PPB;
     if (pi0 >= npairs) return;
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void rbuild_herm_kernel(MstepArgs a, int B, in
 // tol[b] = 1e-14 max_i Re R[i][i] of the freshly built R (chol.hip's pivot threshold).
 __global__ __launch_bounds__(256) void diag_tol_kernel(MstepArgs a, int L) {
     const int b = blockIdx.x;
-    if (a.done && a.done[b]) return;
+    if (mstep_skip(a, b)) return;
     const cd* R = a.R + (size_t)b * L * L;
     __shared__ double red[4];
     double m = 0.0;

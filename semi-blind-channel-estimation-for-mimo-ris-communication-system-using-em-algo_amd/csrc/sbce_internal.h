@@ -301,7 +301,28 @@ struct EstepArgs {
     const double* varn_t = nullptr;   // [B] per-trial noise variances (sbce_ptrs.varn_t), or null
     bool lists_zeroed = false;        // the 5 list counters after list[B*Td] are already 0 (zeroed
                                       // by em_init_kernel / the previous M-step's solve launch)
+    // the moment-repeat rule: the lane that stores a word of mom first loads
+    // the word it overwrites and sets mchg[b] = 1 when any bit differs (null: not armed, nothing
+    // is loaded -- iteration 0 of a call, whose mom holds stale contents, and every E-step some
+    // kernel of which does not carry the fold: estep_momfold_supported)
+    int32_t* mchg = nullptr;          // [B]
 };
+
+// The fold of the moment-repeat rule at a moment store: nonzero when the value about to be stored
+// differs from the stored one in any bit (an integer compare: +0 and -0 differ, a NaN equals
+// itself).
+__device__ __forceinline__ unsigned mom_bits_differ(const cd& u, const cd& v) {
+    const unsigned long long d = ((unsigned long long)__double_as_longlong(u.x) ^
+                                  (unsigned long long)__double_as_longlong(v.x)) |
+                                 ((unsigned long long)__double_as_longlong(u.y) ^
+                                  (unsigned long long)__double_as_longlong(v.y));
+    return (unsigned)(d | (d >> 32));
+}
+// *p = v; armed: the word it overwrites is loaded first and a differing bit OR-ed into chg
+__device__ __forceinline__ void mom_store(cd* p, const cd& v, bool arm, unsigned& chg) {
+    if (arm) chg |= mom_bits_differ(*p, v);
+    *p = v;
+}
 
 // The posterior constants of one noise variance v, in the operation order of the host's scalar
 // path (the launchers' 1 / (varn varn), kSkipThr varn varn, 0.1 varn varn), so that a trial with
@@ -414,7 +435,22 @@ struct MstepArgs {
     // the fixed-point freeze folded into the back substitution of the batched-panel solve: set to 1
     // when the stored theta equals the one it overwrites bit for bit (null: not armed)
     int32_t* freeze_w = nullptr;  // [B]
+    // the moment-repeat rule (armed with freeze_w, and only where every moment writer of the
+    // E-step carries the fold): mchg[b] == 0 after an E-step that compared says that it rewrote
+    // the trial's moments bit for bit, so this M-step would reproduce theta -- every launch skips
+    // the trial (mstep_skip), the back substitution sets freeze_w[b] instead; a live trial's back
+    // substitution clears the word for the next E-step (null: not armed).  mskip is the gate the
+    // launches read: mchg after a comparing E-step, null at a call's iteration 0 (that E-step
+    // compared nothing: every trial changed).
+    int32_t* mchg = nullptr;         // [B]
+    const int32_t* mskip = nullptr;  // [B]
 };
+
+// block-uniform, at the head of every M-step kernel of the batched-panel chain: the trial has
+// stopped, or (moment-repeat rule) its moments are those of the previous iteration
+__device__ __forceinline__ bool mstep_skip(const MstepArgs& a, int b) {
+    return (a.done && a.done[b]) || (a.mskip && !a.mskip[b]);
+}
 
 // Per-trial extents of one tiled-factorisation launch sequence (mstep_large.hip): column
 // blocks at or past col[b] and row tiles at or past row[b] are skipped (null: L); fwd = 0
@@ -484,6 +520,10 @@ hipError_t launch_sup_shift_mom(const Problem& pb, cd* mom, const cd* xsup, cons
 hipError_t launch_ser(const Problem& pb, const cd* xdest, const cd* xtrue, double* out,
                       hipStream_t s);
 hipError_t estep_debug_mfma(unsigned long long* out, int reset);   // SBCE_ESTEP_COUNT=1
+// every kernel launch_estep launches for (pb, mode) that writes moments folds EstepArgs::mchg
+bool estep_momfold_supported(const Problem& pb, int mode);
+// A/B build: trial-M-steps the moment-repeat rule skipped since the last reset (chol.hip)
+hipError_t mstep_debug_momskip(unsigned long long* out, int reset);
 hipError_t estep_debug_sphere(unsigned long long* out3, int reset);   // [enumerated, listed, single path]
 // factorised-weight soft E-step (estep_pair.hip) for the sphere pass's listed symbols
 bool estep_pair_supported(const Problem& pb, int mode);
@@ -497,8 +537,9 @@ hipError_t launch_nmse(const Problem& pb, const cd* theta, const cd* h, double* 
 hipError_t launch_llf(const Problem& pb, const cd* theta, const cd* yp, const cd* up,
                       const cd* yd, const cd* psid, const cd* xd, double* llf, int iters,
                       int it, const int32_t* done, const double* varn_t, hipStream_t s);
-// sbce_em's start in one launch: done[b] = 0, status[b] = status_value, and (cnt) 5 counters = 0
-hipError_t launch_em_init(int B, int32_t* done, int32_t* status, int status_value, int32_t* cnt,
+// sbce_em's start in one launch: done[b] = 0, (mchg) mchg[b] = 0, status[b] = status_value, and
+// (cnt) 5 counters = 0
+hipError_t launch_em_init(int B, int32_t* done, int32_t* mchg, int32_t* status, int status_value, int32_t* cnt,
                           hipStream_t s);
 hipError_t launch_early_stop(const Problem& pb, const cd* theta, const cd* h,
                              int32_t* done, int32_t* iters_done, int it, hipStream_t s);
