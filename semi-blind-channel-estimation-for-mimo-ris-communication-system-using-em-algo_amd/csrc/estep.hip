@@ -1973,7 +1973,13 @@ __global__ __launch_bounds__(256) void estep_tree_kernel(EstepArgs a, PrepConst 
         eb[l] = e;
         db += tb + cabs2(e);
     }
-    const bool ok = pmax <= 1e10 * pmin;                 // ill-conditioned G': to the sweep
+    // ill-conditioned G': to the sweep.  So is a symbol with a pivot of G' that is the ridge alone
+    // (G's own pivot is zero: a zero channel column, H_t = 0): whole classes of hypotheses are
+    // at EXACTLY the same distance, the enumeration's path bounds order them by rounding
+    // (aa = u^2 - reg is not 0), and only the sweep takes the first minimum in product order.
+    // Only these ties are caught: exact ties that leave every pivot above the ridge (two
+    // identical columns, say) are still enumerated
+    const bool ok = pmax <= 1e10 * pmin && pmin > c.reg;
     const double R0 = fmin(d0 - c0, db);
     // single-path check: if along the Babai path every level has exactly one child whose
     // subtree bound is inside R (the Babai child), the Babai point is the only hypothesis

@@ -21,6 +21,11 @@ FOLD = (4, 4, 9, 16, 24, 4)      # L = 36 = 32 + 4: backsub4_kernel<4, true> (re
 EVEN = (4, 2, 10, 16, 24, 4)     # L = 40: backsub4_kernel<2, false>
 GEN = (4, 5, 9, 16, 24, 4)       # L = 36, n_rx > 4: backsub_kernel
 SHAPES = [FOLD, EVEN, GEN]
+# L = 69 > 64 at n_tx = 3, 16-QAM: the batched-panel solve with the tree pass, the enumeration
+# <3, *>, the bounds pass and the listed sweep <3, 3, *, 1> as the folded moment writers.  In
+# test_skipped_msteps_keep_the_chains_bits in hard mode only: no seed 1..40 meets its soft
+# condition (see test_nt3_equals_the_chain for what they gave at 30 dB).
+NT3 = (3, 3, 23, 16, 24, 16)
 SMALL = (2, 2, 8, 16, 24, 4)     # L = 16 <= 64: the one-workgroup M-step (never armed)
 NT2 = (2, 2, 40, 96, 24, 16)     # L = 80: the theta freeze is armed, the n_tx = 2 E-step passes
                                  # carry no fold -- the rule stays unarmed
@@ -32,8 +37,10 @@ B, ITERS = 6, 10
 # iteration 1: -0 against +0 in a lower-triangle entry of S_t) -- bit for bit they changed, and
 # the theta compare freezes those trials one M-step later.  EVEN (n_rx < n_tx: the sweep is the
 # only writer) met the soft condition for none of the seeds 1..12 and for 13, 22, 29, 33, 41.
-SEED_HI = {FOLD: 7, EVEN: 29, GEN: 7}
-MIXED = {FOLD: (9.0, 1), EVEN: (12.0, 1), GEN: (9.0, 3)}     # (dB, seed): frozen and live trials
+SEED_HI = {FOLD: 7, EVEN: 29, GEN: 7, NT3: 7}
+# (dB, seed): frozen and live trials.  NT3, chosen on the device: below 15 dB no trial of the
+# seeds 1..6 stops early; at 15 dB seed 1 stops after [10, 4, 3, 4, 10, 4] iterations.
+MIXED = {FOLD: (9.0, 1), EVEN: (12.0, 1), GEN: (9.0, 3), NT3: (15.0, 1)}
 _cache = {}
 
 
@@ -108,8 +115,10 @@ def _assert_run(res, th, status):
     assert np.array_equal(res["iters_done"], np.full(th.shape[0], ITERS, dtype=np.int32))
 
 
-@pytest.mark.parametrize("mode", ["soft", "hard"])
-@pytest.mark.parametrize("shape", SHAPES, ids=_sid)
+_SKIPPED = [(s, m) for s in SHAPES for m in ("soft", "hard")] + [(NT3, "hard")]
+
+
+@pytest.mark.parametrize("shape,mode", _SKIPPED, ids=[f"{_sid(s)}-{m}" for s, m in _SKIPPED])
 def test_skipped_msteps_keep_the_chains_bits(sbce, shape, mode):
     """30 dB: most trials' moments repeat early.  Product and A/B build equal the chain and the
     conv arm's fixed point; the A/B build skipped at least one M-step per trial that the conv arm
@@ -131,7 +140,39 @@ def test_skipped_msteps_keep_the_chains_bits(sbce, shape, mode):
     assert n >= early
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=_sid)
+@pytest.mark.parametrize("mode", ["soft", "hard"])
+def test_nt3_equals_the_chain(sbce, mode):
+    """NT3 at 30 dB: theta, status and iters_done of the product and the A/B build are the
+    chain's, and the conv arm stops at the same theta.  Seen on the device for every seed 1..40:
+    T_p + T_d = 40 < L = 69 and the posteriors are one-hot, so R is rank deficient (every trial
+    carries SBCE_STATUS_NONHPD, the dropped-pivot solve), the second iteration reproduces the
+    first one's theta bit for bit in all six trials, and the theta compare freezes them there.
+    Hard: the decisions of iteration 1 repeat iteration 0's and the rule skips 6 M-steps (one a
+    trial).  Soft: the moments at theta_0 and theta_1 differ, the rule skips nothing (seed 33: 1)
+    before the freeze -- no seed meets `skipped >= early` of
+    test_skipped_msteps_keep_the_chains_bits in soft mode, so NT3 is in that test in hard mode
+    only.  Its other conditions are asserted here for both modes."""
+    b = _batch(sbce, NT3, 30.0, SEED_HI[NT3])
+    th, status = _chained(sbce, b, mode)
+    assert np.all(np.isfinite(th.view(float)))
+    _assert_run(_plain(sbce, b, mode), th, status)
+    cth, cit = _conv(sbce, b, mode)
+    assert np.array_equal(cth, th)
+    with sbce._lib.debug_env() as lib:
+        _reset(lib)
+        _assert_run(_plain(sbce, b, mode), th, status)
+        n = _skipped(lib)
+    print(f"momfreeze {_sid(NT3)} {mode} 30 dB: fixed point after {cit.tolist()} of {ITERS}, "
+          f"{n} M-steps skipped, status {status.tolist()}")
+    # the seed-dependent conditions of test_skipped_msteps_keep_the_chains_bits, all but soft
+    # mode's `n >= early`: the fold is armed at n_tx = 3 and the <3, *> writers announce a repeat
+    early = int(np.count_nonzero(cit < ITERS))
+    assert 4 * early >= 3 * B
+    if mode == "hard":
+        assert n >= early
+
+
+@pytest.mark.parametrize("shape", SHAPES + [NT3], ids=_sid)
 def test_low_snr_soft_skips_nothing(sbce, shape):
     """0 dB, soft: the posteriors stay spread, no trial's moments repeat -- the folded stores on
     the path that never skips."""
@@ -144,7 +185,7 @@ def test_low_snr_soft_skips_nothing(sbce, shape):
         assert _skipped(lib) == 0
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=_sid)
+@pytest.mark.parametrize("shape", SHAPES + [NT3], ids=_sid)
 def test_mixed_batch_and_batch_independence(sbce, shape):
     """A batch with skipped and live trials: equal to the chain, and each trial run alone (B = 1)
     has the bits it has inside the batch."""
@@ -161,7 +202,7 @@ def test_mixed_batch_and_batch_independence(sbce, shape):
         assert np.array_equal(one["status"], res["status"][i:i + 1]), i
 
 
-@pytest.mark.parametrize("shape", [FOLD, GEN], ids=_sid)
+@pytest.mark.parametrize("shape", [FOLD, GEN, NT3], ids=_sid)
 def test_stale_workspace_never_leaks(sbce, shape):
     """The change words and the moments live in the workspace: a workspace of 0xFF bytes (every
     word set, NaN moments), and what a previous run left behind, change nothing -- iteration 0
