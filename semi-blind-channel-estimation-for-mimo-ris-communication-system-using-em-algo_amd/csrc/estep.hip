@@ -1282,7 +1282,7 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
             const int s3 = lane < NT ? 0 : (lane - NT) % NT;
             const cd xp = s_cons[(best_j >> (k_lm * (NT - 1 - s2))) & mask];
             const cd xq = s_cons[(best_j >> (k_lm * (NT - 1 - s3))) & mask];
-            const cd mv = lane < NT ? xp : cmulc(xp, xq);
+            const cd mv = mom_word(lane < NT ? xp : cmulc(xp, xq));
             out[lane] = mv;
             if (arm && mom_bits_differ(mold, mv)) a.mchg[b] = 1;
         }
@@ -1359,7 +1359,7 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
             }
             const double iz = 1.0 / red[0];
             const double re = red[ire], im = iim >= 0 ? red[iim] : 0.0;
-            const cd mv = cmk(re * iz, (cj ? -im : im) * iz);
+            const cd mv = mom_word(cmk(re * iz, (cj ? -im : im) * iz));
             out[lane] = mv;
             if (arm && mom_bits_differ(mold, mv)) a.mchg[b] = 1;
         }
@@ -2020,10 +2020,10 @@ __global__ __launch_bounds__(256) void estep_tree_kernel(EstepArgs a, PrepConst 
             unsigned chg = 0;
 #pragma unroll
             for (int p2 = 0; p2 < NT; ++p2) {
-                mom_store(mo + p2, xo[p2], arm, chg);
+                mom_store(mo + p2, mom_word(xo[p2]), arm, chg);
 #pragma unroll
                 for (int q = 0; q < NT; ++q)
-                    mom_store(mo + NT + p2 * NT + q, cmulc(xo[p2], xo[q]), arm, chg);
+                    mom_store(mo + NT + p2 * NT + q, mom_word(cmulc(xo[p2], xo[q])), arm, chg);
             }
             if (chg) a.mchg[gsym / c.Td] = 1;            // (b is not kept live this far)
         }
@@ -2238,7 +2238,8 @@ __global__ __launch_bounds__(64 * kBfsWaves) void estep_bfs_kernel(EstepArgs a, 
                     const cd xp = s_cons[(bj >> (lm * (NT - 1 - p2))) & mask];
                     const cd xq = s_cons[(bj >> (lm * (NT - 1 - q))) & mask];
                     unsigned chg = 0;                  // the moment-repeat fold
-                    mom_store(mo + lane, lane < NT ? xp : cmulc(xp, xq), a.mchg != nullptr, chg);
+                    mom_store(mo + lane, mom_word(lane < NT ? xp : cmulc(xp, xq)),
+                              a.mchg != nullptr, chg);
                     if (chg) a.mchg[gsym / c.Td] = 1;
                 }
             } else {
@@ -2287,7 +2288,7 @@ __global__ __launch_bounds__(64 * kBfsWaves) void estep_bfs_kernel(EstepArgs a, 
                             v = caxpy(v, w, lane < NT ? xp : cmulc(xp, xq));
                         }
                     }
-                    const cd mv = cscale(v, 1.0 / z);
+                    const cd mv = mom_word(cscale(v, 1.0 / z));
                     mo[lane] = mv;
                     if (arm && mom_bits_differ(mold, mv)) a.mchg[gsym / c.Td] = 1;
                 }

@@ -320,7 +320,7 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
             }
             const double iz = 1.0 / red[0];
             const double re = red[ire], im = iim >= 0 ? red[iim] : 0.0;
-            mom_store(mout, cmk(re * iz, (cj ? -im : im) * iz), a.mchg != nullptr, chg);
+            mom_store(mout, mom_word(cmk(re * iz, (cj ? -im : im) * iz)), a.mchg != nullptr, chg);
             if (chg) a.mchg[b] = 1;
         }
         if (c.count && lane == 0) atomicAdd(&g_estep_pair, 1ull);

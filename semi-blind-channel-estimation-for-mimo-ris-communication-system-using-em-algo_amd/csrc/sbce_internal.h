@@ -286,7 +286,11 @@ struct EstepArgs {
     const cd* psid;    // [B][Td][P]
     const cd* theta;   // [B][K]
     const cd* cons;    // [M]
-    cd* mom;           // [B][Td][NT + NT*NT]
+    cd* mom;           // [B][Td][NT + NT*NT]; the writers that carry the moment-repeat fold store
+                       // no negative zero (mom_word, armed or not: iteration 0's words are what
+                       // iteration 1 compares against), so equal values are equal bits whichever
+                       // of them wrote the symbol.  The unfolded writers (VALU estep_kernel, the
+                       // n_tx = 2 passes, PM / ZF / MMSE / Gauss) keep the sign they compute.
     const int32_t* done;  // [B] or null
     int32_t* status;   // [B] or null (detector index flag)
     double* prep;      // [B*Td][estep_prep_stride] workspace of the MFMA sweep, or null
@@ -318,6 +322,12 @@ __device__ __forceinline__ unsigned mom_bits_differ(const cd& u, const cd& v) {
                                   (unsigned long long)__double_as_longlong(v.y));
     return (unsigned)(d | (d >> 32));
 }
+// The word a folded writer stores for the value v: v with + 0.0 on both components.  In
+// round-to-nearest that maps -0 to +0 and changes nothing else, so writers that reach the same
+// value by different expressions (x_p conj(x_q) against the conjugate of x_q conj(x_p)) store the
+// same bits.  After a product the addition contracts into the product's FMA (no instruction;
+// only a nonzero product that underflows past the denormals keeps its sign there).
+__device__ __forceinline__ cd mom_word(const cd& v) { return cmk(v.x + 0.0, v.y + 0.0); }
 // *p = v; armed: the word it overwrites is loaded first and a differing bit OR-ed into chg
 __device__ __forceinline__ void mom_store(cd* p, const cd& v, bool arm, unsigned& chg) {
     if (arm) chg |= mom_bits_differ(*p, v);
