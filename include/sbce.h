@@ -455,6 +455,86 @@ int sbce_conv_workspace_bytes(const sbce_dims* d, int want_ll, size_t* bytes);
 int sbce_em_conv(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
                  const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream);
 
+/* ---- Linear soft detection (an additive extension of ABI 7: no existing struct or entry point
+ * changes): per-stream ZF / LMMSE equalisation with a Gaussian soft demapper, for 1..8 streams,
+ * from a GIVEN channel estimate theta.  Per (trial b, data symbol t) with H = H_t the effective
+ * channel of the detector above, rho = sigma2 / es (MMSE) or 0 (ZF), A = H^H H + rho I (Hermitian
+ * n_tx x n_tx, factored by Cholesky), g_a = (A^-1)_aa and z = A^-1 H^H y:
+ *   MMSE  mu_a = 1 - rho g_a,  x_soft_a = z_a / mu_a,  nu_a = es (1 - mu_a) / mu_a
+ *   ZF    x_soft_a = z_a,      nu_a = sigma2 g_a
+ * x_soft is the unbiased estimate of stream a and nu its effective noise variance.  Each stream
+ * is demapped on its own with d_s = |x_soft_a - cons[s]|^2:
+ *   idx_hat[a]   argmin_s d_s, ties to the lowest s;  x_hat = cons[idx_hat]
+ *   post[a][s]   e^{-d_s/nu_a} / sum_s e^{-d_s/nu_a}
+ *   llr[a][i]    log sum_{bit_i = 0} e^{-d_s/nu_a} - log sum_{bit_i = 1} e^{-d_s/nu_a}, with
+ *                bit_i(s) = (labels[s] >> i) & 1; with SBCE_DETECT_MAXLOG
+ *                (min_{bit_i = 1} d_s - min_{bit_i = 0} d_s) / nu_a
+ *   err[b]       the two integer counters of the detector above
+ *   moments      m_a = sum_s post[a][s] cons[s], S[a][a] = sum_s post[a][s] |cons[s]|^2 and
+ *                S[a][c] = m_a conj(m_c) for a != c, in the E-step's layout (m_t, then S_t)
+ * Every sum is min-shifted in the log domain (its smallest member has weight 1), so every output
+ * is finite for any sigma2 > 0, with one exception.  A Cholesky pivot <= 1e-14 max_a A_aa (the
+ * pivot rule of SBCE_SOLVE_CHOL) makes the whole symbol carry no information: x_soft = 0 and
+ * nu = +inf for every stream, so post = 1/M, llr = 0, idx_hat is the table point nearest 0
+ * (lowest index on ties), the moments follow from the uniform post, and the trial gets
+ * SBCE_STATUS_NONHPD; other symbols and trials are unaffected.  A single MMSE stream with
+ * mu_a <= 0 (a zero channel column) is given the same outputs for that stream alone, and no
+ * status bit: its matrix is sound.  Results of a trial do not depend on the batch around it.
+ * Layouts as for the detector above, and
+ *   x_soft [B][T_d][n_tx] complex    nu [B][T_d][n_tx] float64
+ *   moments [B][T_d][n_tx + n_tx^2] complex    status [B] int32 */
+#define SBCE_LINEAR_MMSE 0
+#define SBCE_LINEAR_ZF 1
+
+typedef struct sbce_linear_dims {
+    int32_t batch;      /* B: independent trials (>= 1) */
+    int32_t n_tx;       /* streams (1..8) */
+    int32_t n_rx;       /* receive antennas (1..8; ZF: >= n_tx) */
+    int32_t n_psi;      /* P = rows of PsiTilde_td (>= 1) */
+    int32_t t_d;        /* data symbols (>= 1) */
+    int32_t m;          /* table size (power of two, 2..64) */
+    int32_t kind;       /* SBCE_LINEAR_* */
+    int32_t flags;      /* SBCE_DETECT_MAXLOG; every other bit 0 */
+    double sigma2;      /* > 0: the denominator itself, as sbce_detect_dims.sigma2 */
+    double es;          /* > 0: symbol energy of the MMSE prior (mean |cons|^2; 1 gives the
+                           reference's filter of all_detectorsvsTd.py:71); ignored by ZF */
+} sbce_linear_dims;
+
+typedef struct sbce_linear_ptrs {
+    const void* y_d;
+    const void* psi_d;
+    const void* cons;
+    const void* theta;
+    const int32_t* labels;   /* may be NULL unless llr or err is set */
+    const double* sigma2_t;  /* may be NULL: [B] per-trial sigma2 (values > 0) */
+    const void* x_d_true;    /* may be NULL unless err is set */
+    void* x_soft;            /* may be NULL */
+    double* nu;              /* may be NULL */
+    void* x_hat;             /* may be NULL */
+    int32_t* idx_hat;        /* may be NULL */
+    double* post;            /* may be NULL */
+    double* llr;             /* may be NULL (requires labels) */
+    int32_t* err;            /* may be NULL (requires x_d_true and labels); zeroed by the call */
+    void* moments;           /* may be NULL */
+    int32_t* status;         /* may be NULL: 0 or SBCE_STATUS_NONHPD; zeroed by the call */
+    void* workspace;         /* may be NULL when the workspace query reports 0 */
+    size_t workspace_bytes;
+} sbce_linear_ptrs;
+
+/* Device workspace of the linear detection call for `d` (0 in this version). */
+int sbce_detect_linear_workspace_bytes(const sbce_linear_dims* d, size_t* bytes);
+
+/* One pass over every (trial, data symbol): one small kernel that zeroes `err` and `status` (when
+ * either is set; a kernel where the detector above uses a memset, so that a captured graph holds
+ * kernel nodes only), then one kernel launch, in this order on `hip_stream`; no allocation, no
+ * synchronisation, no floating-point atomic; capturable in a HIP graph.
+ * Decided before any HIP call -- SBCE_EINVAL: null dims / ptrs / required pointer, batch, t_d,
+ * n_psi, n_tx or n_rx < 1, m not a power of two in 2..64, sigma2 <= 0, MMSE with es <= 0, an
+ * unknown kind or flag bit, llr without labels, err without x_d_true or labels, ZF with
+ * n_rx < n_tx, a misaligned pointer (16 bytes complex, 8 float64, 4 int32);
+ * SBCE_EUNSUPPORTED: n_tx > 8 or n_rx > 8; SBCE_EWORKSPACE. */
+int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

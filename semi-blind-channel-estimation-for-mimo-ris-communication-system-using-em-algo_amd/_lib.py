@@ -34,6 +34,8 @@ SBCE_STATUS_SINGULAR = 32
 SBCE_STATUS_NOISE = 64
 SBCE_STATUS_CONVERGED = 128
 SBCE_DETECT_MAXLOG = 1
+SBCE_LINEAR_MMSE = 0
+SBCE_LINEAR_ZF = 1
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_workspace_bytes_solve", "sbce_em",
@@ -42,7 +44,8 @@ EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_detect_workspace_bytes", "sbce_detect",
             "sbce_noise_workspace_bytes", "sbce_noise_var", "sbce_em_noise",
             "sbce_loglik_workspace_bytes", "sbce_loglik", "sbce_conv_workspace_bytes",
-            "sbce_em_conv")
+            "sbce_em_conv",
+            "sbce_detect_linear_workspace_bytes", "sbce_detect_linear")
 
 
 class SbceUnavailable(RuntimeError):
@@ -98,6 +101,24 @@ class DetectPtrs(ctypes.Structure):
                 ("x_hat", ctypes.c_void_p), ("idx_hat", ctypes.c_void_p), ("post", ctypes.c_void_p),
                 ("llr", ctypes.c_void_p), ("err", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
                 ("workspace_bytes", ctypes.c_size_t)]
+
+
+class LinearDims(ctypes.Structure):
+    """sbce_linear_dims (include/sbce.h): ZF / LMMSE soft detection for up to 8 streams."""
+    _fields_ = [("batch", ctypes.c_int32), ("n_tx", ctypes.c_int32), ("n_rx", ctypes.c_int32),
+                ("n_psi", ctypes.c_int32), ("t_d", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("flags", ctypes.c_int32), ("sigma2", ctypes.c_double),
+                ("es", ctypes.c_double)]
+
+
+class LinearPtrs(ctypes.Structure):
+    _fields_ = [("y_d", ctypes.c_void_p), ("psi_d", ctypes.c_void_p), ("cons", ctypes.c_void_p),
+                ("theta", ctypes.c_void_p), ("labels", ctypes.c_void_p),
+                ("sigma2_t", ctypes.c_void_p), ("x_d_true", ctypes.c_void_p),
+                ("x_soft", ctypes.c_void_p), ("nu", ctypes.c_void_p), ("x_hat", ctypes.c_void_p),
+                ("idx_hat", ctypes.c_void_p), ("post", ctypes.c_void_p), ("llr", ctypes.c_void_p),
+                ("err", ctypes.c_void_p), ("moments", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
 class NoiseOpts(ctypes.Structure):
@@ -178,6 +199,12 @@ def load(path=None):
     lib.sbce_detect.restype = ctypes.c_int
     lib.sbce_detect.argtypes = [ctypes.POINTER(DetectDims), ctypes.POINTER(DetectPtrs),
                                 ctypes.c_void_p]
+    lib.sbce_detect_linear_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_detect_linear_workspace_bytes.argtypes = [ctypes.POINTER(LinearDims),
+                                                       ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_detect_linear.restype = ctypes.c_int
+    lib.sbce_detect_linear.argtypes = [ctypes.POINTER(LinearDims), ctypes.POINTER(LinearPtrs),
+                                       ctypes.c_void_p]
     lib.sbce_noise_workspace_bytes.restype = ctypes.c_int
     lib.sbce_noise_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(ctypes.c_size_t)]
     lib.sbce_noise_var.restype = ctypes.c_int

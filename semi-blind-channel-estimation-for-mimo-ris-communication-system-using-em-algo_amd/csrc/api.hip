@@ -864,4 +864,50 @@ int sbce_detect(const sbce_detect_dims* d, const sbce_detect_ptrs* p, void* hip_
     return hip_rc(launch_detect(a, (hipStream_t)hip_stream));
 }
 
+int sbce_detect_linear_workspace_bytes(const sbce_linear_dims* d, size_t* bytes) {
+    if (!d || !bytes) return SBCE_EINVAL;
+    *bytes = 0;                          // a symbol's state lives in LDS and registers
+    return SBCE_OK;
+}
+
+int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, void* hip_stream) {
+    if (!d || !p) return SBCE_EINVAL;
+    if (d->batch < 1 || d->n_tx < 1 || d->n_rx < 1 || d->n_psi < 1 || d->t_d < 1 ||
+        !(d->sigma2 > 0.0) || (d->flags & ~SBCE_DETECT_MAXLOG))
+        return SBCE_EINVAL;
+    if (d->kind != SBCE_LINEAR_MMSE && d->kind != SBCE_LINEAR_ZF) return SBCE_EINVAL;
+    if (d->kind == SBCE_LINEAR_MMSE && !(d->es > 0.0)) return SBCE_EINVAL;
+    if (d->m < 2 || d->m > 64 || (d->m & (d->m - 1))) return SBCE_EINVAL;   // a power of two
+    if (!required({p->y_d, p->psi_d, p->cons, p->theta})) return SBCE_EINVAL;
+    if ((p->llr || p->err) && !p->labels) return SBCE_EINVAL;
+    if (p->err && !p->x_d_true) return SBCE_EINVAL;
+    if (!aligned16(p->x_d_true) || !aligned16(p->x_hat) || !aligned16(p->x_soft) ||
+        !aligned16(p->moments))
+        return SBCE_EINVAL;
+    if (((uintptr_t)p->sigma2_t & 7) || ((uintptr_t)p->post & 7) || ((uintptr_t)p->llr & 7) ||
+        ((uintptr_t)p->nu & 7))
+        return SBCE_EINVAL;
+    if (((uintptr_t)p->labels & 3) || ((uintptr_t)p->idx_hat & 3) || ((uintptr_t)p->err & 3) ||
+        ((uintptr_t)p->status & 3))
+        return SBCE_EINVAL;
+    if (d->kind == SBCE_LINEAR_ZF && d->n_rx < d->n_tx) return SBCE_EINVAL;   // H^H H is singular
+    if (!detect_linear_supported(d->n_tx, d->n_rx)) return SBCE_EUNSUPPORTED;
+    size_t need = 0;
+    sbce_detect_linear_workspace_bytes(d, &need);
+    if (need && (!p->workspace || !aligned16(p->workspace))) return SBCE_EINVAL;
+    if (p->workspace_bytes < need) return SBCE_EWORKSPACE;
+    clear_stale_error();
+    LinearArgs a{};                      // lgM and chunks are launch_detect_linear's
+    a.yd = (const cd*)p->y_d; a.psid = (const cd*)p->psi_d; a.cons = (const cd*)p->cons;
+    a.theta = (const cd*)p->theta; a.labels = p->labels; a.sigma2_t = p->sigma2_t;
+    a.xd = (const cd*)p->x_d_true; a.xsoft = (cd*)p->x_soft; a.nu = p->nu; a.xhat = (cd*)p->x_hat;
+    a.idx = p->idx_hat; a.post = p->post; a.llr = p->llr; a.err = p->err; a.mom = (cd*)p->moments;
+    a.status = p->status;
+    a.B = d->batch; a.NT = d->n_tx; a.NR = d->n_rx; a.P = d->n_psi; a.Td = d->t_d; a.M = d->m;
+    a.kind = d->kind;
+    a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0;
+    a.sigma2 = d->sigma2; a.es = d->es;
+    return hip_rc(launch_detect_linear(a, (hipStream_t)hip_stream));
+}
+
 }  // extern "C"

@@ -1,0 +1,347 @@
+// Linear soft detection (sbce_detect_linear): from a GIVEN channel estimate
+// theta, for every (trial b, data symbol t), per-stream ZF / LMMSE equalisation with a Gaussian
+// soft demapper.  With H = H_t the effective channel of sbce_detect, rho = sigma2 / es (MMSE) or
+// 0 (ZF), A = H^H H + rho I = L L^H, g_a = (A^-1)_aa and z = A^-1 H^H y:
+//   MMSE  mu_a = 1 - rho g_a,  x_soft_a = z_a / mu_a,  nu_a = es (1 - mu_a) / mu_a = sigma2 g_a / mu_a
+//   ZF    x_soft_a = z_a,      nu_a = sigma2 g_a
+// and each stream is demapped on its own: d_s = |x_soft_a - cons[s]|^2, weights e^{-d_s / nu_a}.
+//
+// Work split.  One workgroup of 4 waves takes 32 consecutive symbols of ONE trial.
+//   staging  theta of the trial goes through LDS in tiles of 32 rows of P (32 x 64 x 16 B = 32 KB)
+//            beside the tile's 32 x 32 phases of psi_d (16 KB), both by coalesced 16-byte loads.
+//            Wave w forms H of its 8 symbols: lane = (entry e of the NE = NT NR, symbol subset g);
+//            each sum over p is ONE ascending fma chain.  H then overwrites the staging buffers
+//            (row stride 65: the symbols of a wave fall on different LDS slots).
+//   solve    a group of 8 lanes per symbol (8 symbols per wave).  Lane a owns column a of the
+//            augmented Hermitian matrix [A; (H^H y)^H] and runs a right-looking Cholesky: at
+//            step j the pivot and the scaled column j come from lane j by ds_bpermute, every lane
+//            a > j updates its column, and every lane advances its own forward substitution
+//            L w = e_a with the same column.  Column j is dead after step j, so nothing is kept:
+//            g_a = ||w||^2 and z_a = w^H u accumulate on the way (u = L^-1 H^H y is the augmented
+//            row, broadcast with the column).  No back substitution, no division: pivots by
+//            v_rsq_f64 + two Newton steps (fast_rsqrt64).
+//   demap    lane a scans the table for stream a: minimum and per-bit-class minima, then the
+//            min-shifted sums (the smallest member of every sum has weight 1: nothing is 0/0), the
+//            posterior, its moments and the L-values.
+// Pivot rule (the project's): a pivot <= 1e-14 max_a A_aa fails the whole symbol: x_soft = 0,
+// nu = +inf, so the weights are all 1 (post = 1/M, llr = 0), and the trial gets NONHPD.
+// Determinism: every sum has an order fixed by (NT, NR, P, M) alone, cross-lane moves only copy,
+// the maximum and the integer counters are order-free, no floating-point atomic is used and no
+// workgroup reads another's results: trial b of a B-trial call is bitwise the B = 1 call.
+// Launches: one small kernel that zeroes err and status (when either is set), then the detection
+// kernel: a linear chain of two kernel nodes on the caller's stream, no memset node.
+#include "sbce_internal.h"
+
+namespace sbce {
+
+namespace {
+
+constexpr int kLinThreads = 256;
+constexpr int kLinSym = 32;         // symbols per workgroup: 4 waves x 8 lane groups
+constexpr int kLinPT = 32;          // rows of P per staged tile
+constexpr int kLinMaxNE = 64;       // NT * NR
+constexpr int kLinHS = 65;          // row stride of H_s (one 16-byte slot of padding)
+constexpr int kLinBuf = kLinPT * kLinMaxNE + kLinSym * kLinPT;   // theta tile + psi tile >= 32 * 65
+
+__device__ __forceinline__ cd bperm_c(cd v, int addr) {
+    return cmk(bperm_d(v.x, addr), bperm_d(v.y, addr));
+}
+// max over each group of 8 lanes (quad xor 1, xor 2, then the mirrored quad)
+__device__ __forceinline__ double group8_max(double v) {
+    v = fmax(v, dpp_d<0xB1>(v));
+    v = fmax(v, dpp_d<0x4E>(v));
+    return fmax(v, dpp_d<0x141>(v));
+}
+
+template <int NT>
+__global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a) {
+    __shared__ cd buf_s[kLinBuf];
+    __shared__ cd cons_s[64];
+    __shared__ int lab_s[64];
+    __shared__ int cnt_s[3];        // symbol errors, bit errors, failed-pivot flag
+
+    const int NR = a.NR, P = a.P, Td = a.Td, M = a.M, lgM = a.lgM;
+    const int NE = NT * NR;
+    const int b = blockIdx.x / a.chunks, ch = blockIdx.x % a.chunks;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int t0 = ch * kLinSym;
+    const int tend = t0 + kLinSym < Td ? t0 + kLinSym : Td;
+    const size_t bt = (size_t)b * Td;
+
+    if (tid < M) {
+        cons_s[tid] = a.cons[tid];
+        lab_s[tid] = a.labels ? a.labels[tid] : tid;
+    }
+    if (tid < 3) cnt_s[tid] = 0;
+
+    // ---- staging: H_t of the workgroup's symbols
+    {
+        cd* th_s = buf_s;
+        cd* psi_s = buf_s + kLinPT * kLinMaxNE;
+        const cd* th = a.theta + (size_t)b * P * NE;
+        int lgE = 0;
+        while ((1 << lgE) < NE) ++lgE;
+        const int ng = (64 >> lgE) < 8 ? (64 >> lgE) : 8;   // symbol subsets per wave
+        const int nj = 8 / ng;                              // symbols per lane
+        const int e = lane & ((1 << lgE) - 1), g = lane >> lgE;
+        const bool on = e < NE && g < ng;
+        cd acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = czero();
+        for (int p0 = 0; p0 < P; p0 += kLinPT) {
+            const int np = P - p0 < kLinPT ? P - p0 : kLinPT;
+            __syncthreads();
+            for (int i = tid; i < np * NE; i += kLinThreads) th_s[i] = th[(size_t)p0 * NE + i];
+            for (int i = tid; i < kLinSym * kLinPT; i += kLinThreads) {
+                const int k = i >> 5, pp = i & 31;
+                psi_s[i] = (t0 + k < tend && pp < np) ? a.psid[(bt + t0 + k) * P + p0 + pp] : czero();
+            }
+            __syncthreads();
+            if (on) {
+                const cd* ps = psi_s + (w * 8 + g) * kLinPT;
+                for (int pp = 0; pp < np; ++pp) {
+                    const cd tv = th_s[pp * NE + e];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (j < nj) acc[j] = cfma(acc[j], ps[j * ng * kLinPT + pp], tv);
+                }
+            }
+        }
+        __syncthreads();
+        if (on) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < nj) buf_s[(w * 8 + g + j * ng) * kLinHS + e] = acc[j];
+        }
+        __syncthreads();
+    }
+
+    // ---- solve: 8 lanes per symbol, lane a = column a.  Lanes past NT and groups past the chunk
+    // repeat a valid column (no divergence around the cross-lane moves) and store nothing.
+    const int grp = lane >> 3, al = lane & 7;
+    const int ts = t0 + w * 8 + grp;
+    const bool act = al < NT && ts < tend;
+    const int aa = al < NT ? al : 0;
+    const int k = ts < tend ? w * 8 + grp : tend - 1 - t0;
+    const size_t sym = bt + t0 + k;
+    const cd* Hs = buf_s + k * kLinHS;
+    const double s2 = a.sigma2_t ? a.sigma2_t[b] : a.sigma2;
+    const bool mmse = a.kind == SBCE_LINEAR_MMSE;
+    const double rho = mmse ? s2 / a.es : 0.0;
+
+    cd c[NT + 1];
+#pragma unroll
+    for (int i = 0; i <= NT; ++i) c[i] = czero();
+    for (int r = 0; r < NR; ++r) {
+        const cd ha = Hs[aa * NR + r];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) c[i] = cfmac(c[i], ha, Hs[i * NR + r]);   // conj(H[r][i]) H[r][a]
+        c[NT] = cfmac(c[NT], ha, a.yd[sym * NR + r]);                          // conj((H^H y)_a)
+    }
+    double diag = 0.0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        const bool d = i == aa;
+        c[i].x = d ? c[i].x + rho : c[i].x;
+        diag = d ? c[i].x : diag;
+    }
+    const double tol = 1e-14 * group8_max(diag);
+
+    cd wv[NT];                       // forward substitution L w = e_a, in place
+#pragma unroll
+    for (int i = 0; i < NT; ++i) wv[i] = cmk(i == aa ? 1.0 : 0.0, 0.0);
+    bool fail = false;
+    double g = 0.0;
+    cd z = czero();
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int addr = ((lane & 56) | j) << 2;
+        const double piv = bperm_d(c[j].x, addr);
+        fail = fail || !(piv > tol);
+        const double rinv = fast_rsqrt64(piv);
+        cd lj[NT + 1];
+        cd laj = czero();
+#pragma unroll
+        for (int i = j + 1; i <= NT; ++i) {
+            lj[i] = cscale(bperm_c(c[i], addr), rinv);
+            if (i < NT) laj = csel(i == aa, lj[i], laj);
+        }
+        const cd wj = cscale(wv[j], rinv);
+        g = fma(wj.x, wj.x, g);
+        g = fma(wj.y, wj.y, g);
+        z = cfmac(z, cconj(wj), lj[NT]);                // conj(w_j) u_j, u_j = conj(lj[NT])
+#pragma unroll
+        for (int i = j + 1; i <= NT; ++i) {
+            c[i] = cfmac(c[i], cmk(-lj[i].x, -lj[i].y), laj);
+            if (i < NT) wv[i] = cfma(wv[i], cmk(-lj[i].x, -lj[i].y), wj);
+        }
+    }
+
+    cd xs = z;
+    double nu = s2 * g;
+    bool dead = false;
+    if (mmse) {
+        const double mu = fma(-rho, g, 1.0);
+        const double rmu = 1.0 / mu;
+        xs = cscale(z, rmu);
+        nu *= rmu;
+        dead = !(mu > 0.0);                             // a stream the channel does not carry
+    }
+    dead = dead || fail;                                // fail alone flags the trial
+    if (dead) {
+        xs = czero();
+        nu = INFINITY;
+    }
+    const double inv = dead ? 0.0 : 1.0 / nu;
+
+    // ---- demap of stream a
+    double dmin = INFINITY;
+    int idx = 0;
+    double m0[6], m1[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) m0[i] = m1[i] = INFINITY;
+    for (int s = 0; s < M; ++s) {
+        const double d = cabs2(csub(xs, cons_s[s]));
+        if (d < dmin) {
+            dmin = d;
+            idx = s;
+        }
+        const int lb = lab_s[s];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const bool one = (lb >> i) & 1;
+            m0[i] = one ? m0[i] : fmin(m0[i], d);
+            m1[i] = one ? fmin(m1[i], d) : m1[i];
+        }
+    }
+    double Z = 0.0, saa = 0.0;
+    cd mean = czero();
+    double T0[6], T1[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) T0[i] = T1[i] = 0.0;
+    for (int s = 0; s < M; ++s) {
+        const cd cs = cons_s[s];
+        const double d = cabs2(csub(xs, cs));
+        const double e = fexp_neg(-(d - dmin) * inv);
+        Z += e;
+        mean = caxpy(mean, e, cs);
+        saa = fma(e, cabs2(cs), saa);
+        if (a.llr && !a.maxlog) {
+            const int lb = lab_s[s];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                if (i < lgM) {
+                    const bool one = (lb >> i) & 1;
+                    const double ec = fexp_neg(-(d - (one ? m1[i] : m0[i])) * inv);
+                    T0[i] = one ? T0[i] : T0[i] + ec;
+                    T1[i] = one ? T1[i] + ec : T1[i];
+                }
+            }
+        }
+    }
+    mean = cmk(mean.x / Z, mean.y / Z);
+    saa /= Z;
+
+    const size_t o = sym * NT + aa;
+    if (act) {
+        if (a.xsoft) a.xsoft[o] = xs;
+        if (a.nu) a.nu[o] = nu;
+        if (a.xhat) a.xhat[o] = cons_s[idx];
+        if (a.idx) a.idx[o] = idx;
+        if (a.post)
+            for (int s = 0; s < M; ++s) {
+                const double d = cabs2(csub(xs, cons_s[s]));
+                a.post[o * M + s] = fexp_neg(-(d - dmin) * inv) / Z;
+            }
+        if (a.llr) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+                if (i < lgM) {
+                    double l = (m1[i] - m0[i]) * inv;
+                    if (!a.maxlog) l += log(T0[i]) - log(T1[i]);
+                    a.llr[o * lgM + i] = l;
+                }
+        }
+        if (a.err) {
+            const cd xt = a.xd[o];
+            double bd = INFINITY;
+            int bi = 0;
+            for (int s = 0; s < M; ++s) {
+                const double dx = cabs2(csub(cons_s[s], xt));
+                if (dx < bd) {
+                    bd = dx;
+                    bi = s;
+                }
+            }
+            if (bi != idx) {
+                atomicAdd(&cnt_s[0], 1);
+                atomicAdd(&cnt_s[1], __popc((unsigned)(lab_s[bi] ^ lab_s[idx])));
+            }
+        }
+        if (fail) cnt_s[2] = 1;
+    }
+    if (a.mom) {                     // uniform: the cross-lane moves see every lane
+        cd* mo = a.mom + sym * (NT + NT * NT);
+        if (act) mo[aa] = mean;
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            const cd mq = bperm_c(mean, ((lane & 56) | q) << 2);
+            if (act) mo[NT + aa * NT + q] = q == aa ? cmk(saa, 0.0) : cmulc(mean, mq);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (a.err && (cnt_s[0] | cnt_s[1])) {
+            atomicAdd(&a.err[2 * b], cnt_s[0]);
+            atomicAdd(&a.err[2 * b + 1], cnt_s[1]);
+        }
+        if (a.status && cnt_s[2]) atomicOr(&a.status[b], SBCE_STATUS_NONHPD);
+    }
+}
+
+// err[b][0..1] = 0 and status[b] = 0 (each when set) ahead of the detection kernel's integer adds
+// and ORs.  A kernel, not hipMemsetAsync: in the graph-capture test the memset nodes of this call
+// were observed to leave stale words in err and status on replay (HIP 7.0 runtime; the cause is
+// not established); kernel nodes replayed as captured.
+__global__ __launch_bounds__(256) void linear_zero_kernel(int32_t* err, int32_t* status, int B) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (err && i < 2 * B) err[i] = 0;
+    if (status && i < B) status[i] = 0;
+}
+
+template <int NT>
+hipError_t launch_nt(const LinearArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(detect_linear_kernel<NT>, dim3((unsigned)(a.B * a.chunks)), dim3(kLinThreads),
+                       0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+bool detect_linear_supported(int NT, int NR) { return NT >= 1 && NT <= 8 && NR >= 1 && NR <= 8; }
+
+hipError_t launch_detect_linear(LinearArgs a, hipStream_t s) {
+    a.lgM = 0;
+    while ((1 << a.lgM) < a.M) ++a.lgM;
+    a.chunks = (a.Td + kLinSym - 1) / kLinSym;
+    if ((long long)a.B * a.chunks > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (a.err || a.status) {
+        hipLaunchKernelGGL(linear_zero_kernel, dim3((unsigned)((2LL * a.B + 255) / 256)), dim3(256), 0,
+                           s, a.err, a.status, a.B);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    switch (a.NT) {
+        case 1: return launch_nt<1>(a, s);
+        case 2: return launch_nt<2>(a, s);
+        case 3: return launch_nt<3>(a, s);
+        case 4: return launch_nt<4>(a, s);
+        case 5: return launch_nt<5>(a, s);
+        case 6: return launch_nt<6>(a, s);
+        case 7: return launch_nt<7>(a, s);
+        case 8: return launch_nt<8>(a, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace sbce

@@ -594,6 +594,34 @@ struct DetectArgs {
 bool detect_supported(int NT, int NR, int M);   // hyp_enum.h's limits: 1..4, 1..8, M^NT <= 65536
 hipError_t launch_detect(DetectArgs a, hipStream_t s);
 
+// Linear soft detection (detect_linear.hip, sbce_detect_linear): the detection kernel, preceded by
+// a small zeroing kernel when err or status is set
+struct LinearArgs {
+    const cd* yd;      // [B][Td][NR]
+    const cd* psid;    // [B][Td][P]
+    const cd* cons;    // [M]
+    const cd* theta;   // [B][P*NT*NR]
+    const int32_t* labels;    // [M] or null
+    const double* sigma2_t;   // [B] or null
+    const cd* xd;      // [B][Td][NT] or null
+    cd* xsoft;         // [B][Td][NT] or null
+    double* nu;        // [B][Td][NT] or null
+    cd* xhat;          // [B][Td][NT] or null
+    int32_t* idx;      // [B][Td][NT] or null
+    double* post;      // [B][Td][NT][M] or null
+    double* llr;       // [B][Td][NT][lgM] or null
+    int32_t* err;      // [B][2] or null (zeroed before the launch)
+    cd* mom;           // [B][Td][NT + NT*NT] or null
+    int32_t* status;   // [B] or null (zeroed before the launch)
+    int B, NT, NR, P, Td, M;
+    int lgM, chunks;   // set by launch_detect_linear: log2 M, workgroups per trial
+    int kind;          // SBCE_LINEAR_*
+    int maxlog;        // llr holds the max-log L-values
+    double sigma2, es;
+};
+bool detect_linear_supported(int NT, int NR);   // 1..8, 1..8
+hipError_t launch_detect_linear(LinearArgs a, hipStream_t s);
+
 // Noise-variance update (noise.hip, sbce_noise_var / sbce_em_noise): two launches per update
 struct NoiseArgs {
     const cd* yd;      // [B][Td][NR]

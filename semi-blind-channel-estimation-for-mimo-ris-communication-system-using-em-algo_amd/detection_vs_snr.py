@@ -25,15 +25,19 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-replay", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--detector", choices=["ml", "mmse", "zf"], default="ml",
+                    help="joint ML (n_tx <= 4) or per-stream LMMSE / ZF soft detection (n_tx <= 8)")
     a = ap.parse_args()
     init_distributed()
     pkg = package()
     x, ser, ber, nmse = pkg.sweeps.detection_vs_snr(
         tuple(a.SNR), a.T_d, a.T_p, a.N, a.n_rx, a.n_tx, a.itera, a.monte_iter, a.M,
-        tuple(a.estimators), a.power, a.seed, replay=not a.no_replay, noise=a.noise)
+        tuple(a.estimators), a.power, a.seed, replay=not a.no_replay, noise=a.noise,
+        detector=a.detector)
     curves = {f"SER {e}": v for e, v in ser.items()}
     curves.update({f"BER {e}": v for e, v in ber.items()})
-    report("SNR", x, curves, a.out, "ML detection per channel estimate", ylabel="error rate",
+    title = {"ml": "ML", "mmse": "LMMSE", "zf": "ZF"}[a.detector]
+    report("SNR", x, curves, a.out, f"{title} detection per channel estimate", ylabel="error rate",
            logy=True)
     report("SNR", x, {f"NMSE {e}": v for e, v in nmse.items()})
 

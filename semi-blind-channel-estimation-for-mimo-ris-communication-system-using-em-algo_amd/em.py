@@ -826,6 +826,114 @@ def detect(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, labels=None, X
     return {k: v[0] for k, v in r.items()}
 
 
+_WANT_LINEAR = ("x_soft", "nu", "x_hat", "idx", "llr", "post")
+_WANT_LINEAR_ALL = _WANT_LINEAR + ("moments", "status")
+_LINEAR_KINDS = {"mmse": _lib.SBCE_LINEAR_MMSE, "zf": _lib.SBCE_LINEAR_ZF}
+
+
+def _detect_linear_call(torch, Yd, Ps, Cs, Th, n_tx, kind, sigma2, sigma2_t, es, lab, Xd, maxlog,
+                        want):
+    """One sbce_detect_linear on device tensors; returns the dict of device outputs."""
+    lib = _lib.load()
+    B, T_d, n_rx = Yd.shape
+    P, M = Ps.shape[2], Cs.shape[0]
+    if Ps.shape != (B, T_d, P) or Th.shape != (B, P * n_tx * n_rx):
+        raise ValueError("detect_linear: inconsistent shapes")
+    if kind not in _LINEAR_KINDS:
+        raise ValueError("kind must be 'mmse' or 'zf'")
+    lgM = max(int(M - 1).bit_length(), 1)
+    bad = set(want) - set(_WANT_LINEAR_ALL)
+    if bad:
+        raise ValueError(f"unknown outputs {sorted(bad)}")
+    c128, f64, i32 = torch.complex128, torch.float64, torch.int32
+    shapes = {"x_soft": ((B, T_d, n_tx), c128), "nu": ((B, T_d, n_tx), f64),
+              "x_hat": ((B, T_d, n_tx), c128), "idx": ((B, T_d, n_tx), i32),
+              "post": ((B, T_d, n_tx, M), f64), "llr": ((B, T_d, n_tx, lgM), f64),
+              "moments": ((B, T_d, n_tx + n_tx * n_tx), c128), "status": ((B,), i32)}
+    out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device="cuda")
+           for k in _WANT_LINEAR_ALL if k in want}
+    if Xd is not None and lab is not None:
+        out["err"] = torch.empty((B, 2), dtype=i32, device="cuda")
+
+    def ptr(k):
+        return out[k].data_ptr() if k in out else None
+
+    dims = _lib.LinearDims(B, n_tx, n_rx, P, T_d, M, _LINEAR_KINDS[kind],
+                           _lib.SBCE_DETECT_MAXLOG if maxlog else 0, float(sigma2), float(es))
+    nb = ctypes.c_size_t(0)
+    _lib.check(lib.sbce_detect_linear_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
+               "sbce_detect_linear_workspace_bytes")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device="cuda") if nb.value else None
+    ptrs = _lib.LinearPtrs(Yd.data_ptr(), Ps.data_ptr(), Cs.data_ptr(), Th.data_ptr(),
+                           lab.data_ptr() if lab is not None else None,
+                           sigma2_t.data_ptr() if sigma2_t is not None else None,
+                           Xd.data_ptr() if Xd is not None else None,
+                           ptr("x_soft"), ptr("nu"), ptr("x_hat"), ptr("idx"), ptr("post"),
+                           ptr("llr"), ptr("err"), ptr("moments"), ptr("status"),
+                           ws.data_ptr() if ws is not None else None, nb.value)
+    _lib.check(lib.sbce_detect_linear(dims, ptrs, torch.cuda.current_stream().cuda_stream),
+               "sbce_detect_linear")
+    return out
+
+
+def _linear_es(torch, cons, es):
+    """The MMSE prior's symbol energy: the given value, or mean |cons|^2 of the table (taken on
+    the host from an array; a device tensor costs one synchronising copy)."""
+    if es is not None:
+        return float(es)
+    c = cons.cpu().numpy() if isinstance(cons, torch.Tensor) else np.asarray(cons)
+    return float(np.mean(np.abs(c) ** 2))
+
+
+def detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind="mmse", es=None, labels=None,
+                        x_d_true=None, noise="em", maxlog=False, want=_WANT_LINEAR,
+                        return_device=False):
+    """Linear soft detection of a batch of trials from a channel estimate, for n_tx = 1..8: ONE
+    sbce_detect_linear call (the detection kernel of csrc/detect_linear.hip, preceded by a small
+    zeroing kernel when err or status is produced).
+
+    Arguments as detect_batch.  kind: 'mmse' (LMMSE equaliser with the prior energy ``es``; None
+    means mean |cons|^2, 1 gives the reference's filter of all_detectorsvsTd.py:71) or 'zf' (needs
+    n_rx >= n_tx).  Returns a dict with the outputs named in ``want``: x_soft (B,T_d,n_tx) the
+    unbiased per-stream estimate and nu its effective noise variance; x_hat / idx the per-stream
+    nearest table point; post (B,T_d,n_tx,M) and llr (B,T_d,n_tx,log2 M) of the Gaussian demapper
+    (exact or, maxlog=True, max-log); moments (B,T_d,n_tx+n_tx^2) in estep_batch's layout; status
+    (B,) int32, SBCE_STATUS_NONHPD where a symbol's matrix had a failed pivot (that symbol:
+    x_soft = 0, nu = inf, post = 1/M, llr = 0); with x_d_true also err (B,2) int32."""
+    torch = _torch()
+    es = _linear_es(torch, cons, es)                   # from the caller's table, before the upload
+    Yd, Ps, Cs, Th, Xd = (_cdev(torch, x) for x in (y_d, psi_d, cons, theta, x_d_true))
+    lab = _detect_labels(Cs.shape[0], labels, "llr" in want or Xd is not None)
+    lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
+    s2, s2t = _sigma2_arg(torch, varn, Yd.shape[0], noise)
+    out = _detect_linear_call(torch, Yd, Ps, Cs, Th, int(n_tx), kind, s2, s2t, es, lab_d, Xd,
+                              maxlog, tuple(want))
+    return _result(torch, out, return_device)
+
+
+def detect_linear(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, kind="mmse", es=None,
+                  labels=None, X_d=None, noise="em", maxlog=False, want=_WANT_LINEAR):
+    """detect_linear_batch for one trial in the reference's list layouts (as detect()).
+    all_possibleSymbols may also be the (M,) table itself (the M^n_tx hypothesis table is never
+    enumerated here and is out of reach at n_tx = 8); n_tx then follows from theta's length.
+    Returns the dict of detect_linear_batch without the batch axis."""
+    aps = np.asarray(all_possibleSymbols)
+    T_d = len(Y_d)
+    y = np.stack([np.asarray(v).reshape(-1) for v in Y_d])[None]
+    psi = np.asarray(PsiTilde_td)[:, :T_d].T[None]
+    if aps.ndim == 1:
+        cons = aps[:int(M)].astype(complex)
+        n_tx = np.asarray(theta).size // (psi.shape[2] * y.shape[2])
+    else:
+        n_tx = aps.shape[1]
+        cons = cons_from_aps(aps, int(M))
+    xt = None if X_d is None else np.stack([np.asarray(x).reshape(-1) for x in X_d[:T_d]])[None]
+    r = detect_linear_batch(y, psi, cons, np.asarray(theta, dtype=complex).reshape(1, -1), varn,
+                            n_tx, kind=kind, es=es, labels=labels, x_d_true=xt, noise=noise,
+                            maxlog=maxlog, want=want)
+    return {k: v[0] for k, v in r.items()}
+
+
 def ser_batch(x_dest, x_d_true):
     """Per-trial SER on the device (sbce_ser): (ser_reference, ser_elementwise), the first
     being the expression of PMd/SER/log_max_SER.py:162."""
@@ -981,7 +1089,8 @@ class EMEngine:
                                   device="cuda")
         self.ws = self.ws_all[:max(whole, 16)]
         self.x_d = _cdev(torch, x_d_true)
-        self.mom = torch.zeros((B, T_d, self.n_tx + self.n_tx ** 2), dtype=torch.complex128,
+        self.es_table = _linear_es(torch, batch["cons"], None)   # detect_linear's default prior
+        self.mom =torch.zeros((B, T_d, self.n_tx + self.n_tx ** 2), dtype=torch.complex128,
                                device="cuda")
         self.x_sup = _cdev(torch, x_sup)
         if early_stop and self.h is None:
@@ -1080,6 +1189,21 @@ class EMEngine:
         s2, s2t = _sigma2_arg(torch, (self.varn, self.varn_t), self.B, noise)
         out = _detect_call(torch, self.y_d, self.psi_d, self.cons, self.theta, self.n_tx, s2, s2t,
                            lab_d, xd, maxlog, tuple(want))
+        return _result(torch, out, return_device)
+
+    def detect_linear(self, kind="mmse", es=None, labels=None, x_d_true=None, noise="em",
+                      maxlog=False, want=_WANT_LINEAR, return_device=False):
+        """One sbce_detect_linear on the engine's resident y_d, psi_d, cons and CURRENT theta, on
+        the current stream: the outputs of detect_linear_batch (n_tx up to 8).  x_d_true defaults
+        to the engine's own."""
+        torch = self.torch
+        xd = self.x_d if x_d_true is None else _cdev(torch, x_d_true)
+        lab = _detect_labels(self.M, labels, "llr" in want or xd is not None)
+        lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
+        s2, s2t = _sigma2_arg(torch, (self.varn, self.varn_t), self.B, noise)
+        out = _detect_linear_call(torch, self.y_d, self.psi_d, self.cons, self.theta, self.n_tx,
+                                  kind, s2, s2t, self.es_table if es is None else float(es), lab_d,
+                                  xd, maxlog, tuple(want))
         return _result(torch, out, return_device)
 
     def nmse(self):

@@ -39,7 +39,7 @@ import numpy as np
 from . import signal_model as sm
 from .distributed import Accumulators, shard
 from .em import (em_batch, em_approx_batch, ser_batch, gauss_expand_batch, nmse_batch,
-                 detect_batch, em_batch_noise, em_batch_conv, _GAUSS_CONS)
+                 detect_batch, detect_linear_batch, em_batch_noise, em_batch_conv, _GAUSS_CONS)
 from .qam import qam_constellation, gray_labeling
 
 
@@ -408,7 +408,7 @@ DETECT_ESTIMATORS = ("pilot", "soft", "hard", "pm", "zf", "mmse", "genie")
 def detection_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2, itera=5,
                      monte_iter=15, M=4, estimators=DETECT_ESTIMATORS, power=10.0, seed=0,
                      replay=True, varh=1.0, partition_r=1, noise="em", labels=None,
-                     batch_snr=True):
+                     batch_snr=True, detector="ml"):
     """Uncoded SER and BER (and NMSE) per SNR of the joint ML detector (sbce_detect) fed each
     estimator's channel, on gen_snr's data (the layout of PMd/SNR/all_Detectors.py:362-370):
     'pilot' = the pilot-only start h0, 'genie' = the true h, every other name an em_batch mode
@@ -416,12 +416,23 @@ def detection_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n
     per-trial symbol and bit error counts come from the device counters and are accumulated as
     extras, all-reduced ONCE with the NMSE sums.  noise: the detector's sigma^2 ('em' varn^2,
     'true' varn); labels: the bit labelling (default qam.gray_labeling).
+    detector: 'ml' (sbce_detect, n_tx <= 4), or the linear receivers 'mmse' / 'zf'
+    (sbce_detect_linear, prior energy mean |cons|^2), which take n_tx up to 8 with the estimators
+    pilot, genie, pm, pm_soft, zf and mmse; soft and hard keep the exact E-step's own limit
+    (n_tx <= 4, M^n_tx <= 2^24) and raise ValueError beyond it.
     Returns (SNR, ser {est: curve}, ber {est: curve}, nmse {est: curve})."""
     estimators = tuple(estimators)
     bad = [e for e in estimators if e not in ("pilot", "genie", "soft", "hard", "pm", "pm_soft",
                                               "zf", "mmse")]
     if bad:
         raise ValueError(f"unknown estimators {bad}")
+    if detector not in ("ml", "mmse", "zf"):
+        raise ValueError("detector must be 'ml', 'mmse' or 'zf'")
+    if detector != "ml" and (n_tx > 4 or M ** n_tx > 1 << 24):
+        beyond = [e for e in estimators if e in ("soft", "hard")]
+        if beyond:
+            raise ValueError(f"estimators {beyond} enumerate M^n_tx hypotheses: n_tx <= 4 and "
+                             f"M^n_tx <= 2^24 (n_tx = {n_tx}, M = {M})")
     dist, world, rank = _dist()
     mine = shard(monte_iter, world, rank).tolist()
     points, varns = gen_snr(SNR, T_d, T_p, N, n_rx, n_tx, monte_iter, M, power, seed, replay,
@@ -442,8 +453,13 @@ def detection_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n
                 theta = em_batch(b["y_d"], b["y_p"], b["psi_d"], b["u_p"], cons, vn, itera,
                                  b["theta0"], mode=est,
                                  partition_r=partition_r if est.startswith("pm") else 0)["theta"]
-            r = detect_batch(b["y_d"], b["psi_d"], cons, theta, vn, n_tx, labels=lab,
-                             x_d_true=x_true, noise=noise, want=())
+            if detector == "ml":
+                r = detect_batch(b["y_d"], b["psi_d"], cons, theta, vn, n_tx, labels=lab,
+                                 x_d_true=x_true, noise=noise, want=())
+            else:
+                r = detect_linear_batch(b["y_d"], b["psi_d"], cons, theta, vn, n_tx,
+                                        kind=detector, labels=lab, x_d_true=x_true, noise=noise,
+                                        want=())
             nm = _nmse(np.asarray(theta), b["h"])
             for k, o0, o1 in zip(ks, off[:-1], off[1:]):
                 acc.add(ei * ns + k, nm[o0:o1], extra_values=r["err"][o0:o1])
