@@ -1755,7 +1755,7 @@ hipError_t launch_chol_batched(const Problem& pb, const MstepArgs& a, hipStream_
     // the wide schedule: even panels j >= 2 update panels j and j+1 by [0, jb) in one launch
     // (panel_update2_kernel), odd panels are pre-updated by panel j-1 inside their factor launch:
     // half the left-looking HBM re-reads of one update launch per panel
-    const bool g3 = g_debug.cplx3 && (a.solve_mode == SBCE_SOLVE_CHOL || a.solve_mode == kSolveClampHpd);
+    const bool g3 = gauss_products(a.solve_mode);
     for (int j = 0; j < nfac; ++j) {
         const int jb = j * PW;
         const int rem = (pb.L - jb + NB - 1) / NB;

@@ -409,7 +409,7 @@ __device__ __forceinline__ void mstep_small_body(const MstepArgs& a, int NT, int
 #pragma unroll
             for (int k = 0; k < YK; ++k)
                 if (yl[k] == c) {
-                    Y[k] = cscale(Y[k], iv);
+                    Y[k] = cscale_x(Y[k], iv);
                     row[64 + (tid + kSmallThreads * k - c * NR)] = Y[k];
                 }
             __syncthreads();
@@ -765,8 +765,8 @@ __global__ __launch_bounds__(64) void mstep_small2_solve_kernel(MstepArgs a, int
         iv_n = dinv[cp];
         lcr_n = sL[cp * LDR + (r & 31)];
         if (r == c) {
-            Y[0] = cscale(Y[0], iv);
-            Y[1] = cscale(Y[1], iv);
+            Y[0] = cscale_x(Y[0], iv);
+            Y[1] = cscale_x(Y[1], iv);
         }
         cd xc[NR];
 #pragma unroll
@@ -975,8 +975,8 @@ __global__ __launch_bounds__(64) void mstep_small3_solve_kernel(MstepArgs a, int
         iv_n = dinv[cp];
         lcr_n = sL[cp * LDR + (r & 31)];
         if (r == c) {
-            Y[0] = cscale(Y[0], iv);
-            Y[1] = cscale(Y[1], iv);
+            Y[0] = cscale_x(Y[0], iv);
+            Y[1] = cscale_x(Y[1], iv);
         }
         cd xc[NR];
 #pragma unroll

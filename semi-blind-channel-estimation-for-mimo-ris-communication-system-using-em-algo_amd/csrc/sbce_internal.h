@@ -19,10 +19,10 @@ typedef double2 cd;
 // the accumulators X1 = C_re - P1 (cre), X2 = -P2 (c2), X3 = C_im + C_re - P3 (cim, csub_init)
 // give re = X1 + X2, im = X3 - X1 + X2 (csub_out).  The rounding of the imaginary part grows
 // (error ~ eps (|ar| + |ai|)(|br| + |bi|)), so G3 is used where no rank decision reads the
-// result: the CHOL solve, and in the min-norm solve AFTER the rank cut (the Gram build C = G^H G,
-// minnorm.hip gram_kernel, and C's own tiled factorisation).  Never for R's factorisation in the
-// drop or min-norm paths: its pivots past the numerical rank ARE the rounding noise, and the
-// pivot decisions must see four-MFMA rounding.
+// result: the CHOL / CHOL_DROP solve (one solve, one route: gauss_products below), and in the
+// min-norm solve AFTER the rank cut (the Gram build C = G^H G, minnorm.hip gram_kernel, and C's
+// own tiled factorisation).  Never for R's factorisation in the min-norm path: its pivots past
+// the numerical rank ARE the rounding noise, and the rank decision must see four-MFMA rounding.
 typedef double mf4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ mf4 mfma4(double a, double b, mf4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -59,6 +59,10 @@ __device__ __forceinline__ cd cadd(cd a, cd b) { return cmk(a.x + b.x, a.y + b.y
 __device__ __forceinline__ cd csub(cd a, cd b) { return cmk(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ cd cconj(cd a) { return cmk(a.x, -a.y); }
 __device__ __forceinline__ cd cscale(cd a, double s) { return cmk(a.x * s, a.y * s); }
+// x_c = y_c iv of a back substitution, as y_c iv + (+0): the product's bits for every iv != 0, and
+// +0 for a dropped unknown (iv = 0) whatever the sign of the y_c it discards, so theta = conj(x)
+// is (+0, -0) there as oracle.em_reduced.mstep_chol_policy's and depends on no discarded sign
+__device__ __forceinline__ cd cscale_x(cd a, double s) { return cmk(fma(a.x, s, 0.0), fma(a.y, s, 0.0)); }
 __device__ __forceinline__ cd cmul(cd a, cd b) {
     return cmk(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
 }
@@ -400,6 +404,13 @@ constexpr double kPairDmax = 640.0;
 // never meets a non-PSD Schur complement).  R's own factorisations never clamp: in every
 // public mode a pivot at or below 1e-14 max diag R is dropped (see SBCE_SOLVE_CHOL, sbce.h).
 constexpr int kSolveClampHpd = 16;
+// Complex tile products from three real MFMAs (Gauss; SBCE_CPLX3=0: four) in every factorisation
+// but the min-norm solve's first.  CHOL and CHOL_DROP are one solve and take one route: theta
+// is bitwise the same under both (test_planted_pivots_are_dropped_exactly_where_planted).
+inline bool gauss_products(int solve_mode) {
+    return g_debug.cplx3 && (solve_mode == SBCE_SOLVE_CHOL || solve_mode == SBCE_SOLVE_CHOL_DROP ||
+                             solve_mode == kSolveClampHpd);
+}
 
 struct MstepArgs {
     const cd* yd;
