@@ -198,6 +198,34 @@ int sbce_workspace_bytes_solve(const sbce_dims* d, int solve_mode, size_t* bytes
 int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode,
             int solve_mode, void* hip_stream);
 
+/* sbce_em on n = 1..8 independent problems at once (the stream sub-batches of one batch, or
+ * unrelated calls), problem j on hip_streams[j], issued iteration by iteration over all of them --
+ * and no longer than needed: where sbce_em's fixed-point rule applies (above) and the stream is
+ * not being captured, the launch sequence of a problem ENDS once every one of its trials has
+ * reached its fixed point.  The back substitution that freezes a problem's last live trial stores
+ * a per-call generation number to a word of host-mapped memory; before issuing iteration
+ * it >= lead the call waits for the event it recorded after iteration it - lead and reads the
+ * word.  Every iteration after that point would touch nothing, so theta, status, x_dest and
+ * iters_done (= iters) are bit for bit those of sbce_em; `lead` - 1 empty iterations are issued
+ * instead of all the remaining ones.
+ *   lead            1..iters: iterations the host may run ahead of the device; 0: the library's
+ *                   default (2, or iters when smaller).
+ *   iters_issued    host array [n] or NULL: iterations enqueued per problem (iters wherever the
+ *                   rule does not apply, the stream is capturing or no end was seen).
+ * Every stream of hip_streams must belong to the calling thread's CURRENT device (hipSetDevice):
+ * the events and the counter of a paced problem are made on that device.
+ * The call returns when everything is enqueued and does not synchronise at its end; outputs are
+ * stream-ordered as sbce_em's.  UNLIKE sbce_em IT MAY BLOCK THE CALLING THREAD for up to the
+ * duration of the run: it waits for events of its own, already enqueued launches (never for the
+ * word itself, so never longer than the device works).  The pinned word, the device counter and
+ * the events come from a small pool the library owns; a steady-state call allocates nothing.
+ * Every argument of every problem is checked as sbce_em checks it before any HIP call: on
+ * SBCE_EINVAL / SBCE_EUNSUPPORTED / SBCE_EWORKSPACE nothing was issued for any problem.
+ * SBCE_EINVAL also: n outside 1..8, a null array, lead < 0 or lead > iters. */
+int sbce_em_multi(int n, const sbce_dims* const* dims, const sbce_ptrs* const* ptrs, int iters,
+                  int estep_mode, int solve_mode, void* const* hip_streams, int lead,
+                  int* iters_issued);
+
 /* One E-step: theta -> per-symbol posterior moments, written to `moments`
  * [B][T_d][n_tx + n_tx*n_tx] complex (m_t, then S_t row-major,
  * S_t[a][b] = E[x_a conj(x_b)]).  Test/diagnostic entry point for the

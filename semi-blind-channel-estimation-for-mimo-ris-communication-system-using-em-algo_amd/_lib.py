@@ -38,7 +38,7 @@ SBCE_LINEAR_MMSE = 0
 SBCE_LINEAR_ZF = 1
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
-            "sbce_workspace_bytes_solve", "sbce_em",
+            "sbce_workspace_bytes_solve", "sbce_em", "sbce_em_multi",
             "sbce_estep", "sbce_mstep", "sbce_ser", "sbce_gauss_expand", "sbce_nmse",
             "sbce_approx_workspace_bytes", "sbce_approx_em",
             "sbce_detect_workspace_bytes", "sbce_detect",
@@ -172,6 +172,11 @@ def load(path=None):
     lib.sbce_em.restype = ctypes.c_int
     lib.sbce_em.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
                             ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.sbce_em_multi.restype = ctypes.c_int
+    lib.sbce_em_multi.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.POINTER(Dims)),
+                                  ctypes.POINTER(ctypes.POINTER(Ptrs)), ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_int)]
     lib.sbce_estep.restype = ctypes.c_int
     lib.sbce_estep.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
                                ctypes.c_void_p, ctypes.c_void_p]

@@ -7,7 +7,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <initializer_list>
+#include <mutex>
+#include <vector>
 
 #include "sbce_internal.h"
 
@@ -354,105 +357,147 @@ int sbce_workspace_bytes_solve(const sbce_dims* d, int solve_mode, size_t* bytes
     return SBCE_OK;
 }
 
-// The EM loop of sbce_em, sbce_em_noise and sbce_em_conv.  nz == nullptr: sbce_em.  nz: the noise
-// parameter is estimated (noise.hip): nz->varn_est is the E-step's per-trial parameter, updated
-// after every M-step, and the oracle early stop runs after the update in its own launch.  cv: the
-// truth-free stop (loglik.hip) closes every iteration and owns the `done` flags; with cv absent
-// the launches are exactly those of the loop without it.
-static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
-                  const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream) {
-    clear_stale_error();
+}  // extern "C"
+
+namespace {
+
+// The EM loop of sbce_em, sbce_em_noise, sbce_em_conv and sbce_em_multi as a chain on one struct:
+// check() decides everything that needs no HIP call, begin() issues what precedes the loop,
+// iteration(it) one iteration, finish() the decisions launch and the iters_done fill.
+// nz == nullptr: sbce_em.  nz: the noise parameter is estimated (noise.hip): nz->varn_est is the
+// E-step's per-trial parameter, updated after every M-step, and the oracle early stop runs after
+// the update in its own launch.  cv: the truth-free stop (loglik.hip) closes every iteration and
+// owns the `done` flags; with cv absent the launches are exactly those of the loop without it.
+struct EmChain {
+    const sbce_ptrs* p = nullptr;
+    const sbce_noise_opts* nz = nullptr;
+    const sbce_conv_opts* cv = nullptr;
+    int iters = 0, estep_mode = 0, solve_mode = 0;
+    hipStream_t s = nullptr;
     Problem pb;
-    if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
-    if ((nz || cv) && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
-    if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
-    if (!valid_solve(solve_mode)) return SBCE_EINVAL;
-    int rc = check_ptrs(p, pb, true, solve_mode);
-    if (rc) return rc;
-    if (p->llf && !p->x_d_true) return SBCE_EINVAL;
-    const bool gauss = estep_mode == SBCE_ESTEP_GAUSS;
-    if (gauss && !(pb.varx > 0.0)) return SBCE_EINVAL;
-    const bool hard = estep_mode == SBCE_ESTEP_HARD || estep_mode == SBCE_ESTEP_ZF ||
-                      estep_mode == SBCE_ESTEP_MMSE;
-    if (p->x_dest && (!hard || !aligned16(p->x_dest))) return SBCE_EINVAL;
-    if (p->x_sup && ((estep_mode != SBCE_ESTEP_SOFT && estep_mode != SBCE_ESTEP_HARD) ||
-                     !aligned16(p->x_sup)))
-        return SBCE_EINVAL;
-    if (nz && (rc = check_noise(p, nz, pb))) return rc;
-    if (cv && (rc = check_conv(p, cv, pb))) return rc;
-    if (pb.B == 0 || iters == 0) return SBCE_OK;
-    hipStream_t s = (hipStream_t)hip_stream;
-    const Carve c = carve(pb, solve_mode);
-    char* ws = (char*)p->workspace;
-    int32_t* done = (int32_t*)(ws + c.done);
-    const bool early = p->h_true != nullptr;
-    // L <= 64: the whole M-step in one launch (BASELINE cfg 5: L = 32)
-    const bool small = mstep_small_supported(pb, solve_mode) && !(gauss && pb.NR == 1);
-    // n_tx <= 2 small path: its solve launch zeroes the E-step's list counters for the next
-    // iteration, em_init_kernel for the first -- no counter memset per E-step
-    const bool small2 = small && mstep_small2_selected(pb);
-    int32_t* list_cnt = c.has_prep ? (int32_t*)(ws + c.list) + (size_t)pb.B * pb.Td : nullptr;
-
-    // The fixed-point freeze: the plain chain is a pure function of theta per
-    // trial, so once the back substitution stores the theta it overwrites bit for bit, the trial's
-    // later iterations would repeat this one -- the back substitution flags the trial and the
-    // kernels skip it.  Armed only where theta is the whole state and nothing reads it per
-    // iteration: not with the noise estimate, the conv stop (it owns the flags), the oracle stop
-    // (iters_done counts executed iterations), the LLF history or superimposed pilots, and only
-    // on the batched-panel solve, whose back substitutions carry the fold.
-    const bool freeze = !nz && !cv && !early && !p->llf && !p->x_sup && !small &&
-                        chol_batched_selected(pb, solve_mode);
-    // The moment-repeat rule: the M-step is a pure function of the moments and
-    // the call's constant inputs, so a trial whose E-step rewrote its moments bit for bit is at
-    // its fixed point one M-step before the theta compare sees it.  The moment stores of the
-    // E-step flag a change in mchg[b]; the M-step's launches skip a trial without one and the
-    // back substitution freezes it.  Armed with the freeze, and only where every moment writer of
-    // the launched E-step carries the fold.
-    const bool momfreeze = freeze && estep_momfold_supported(pb, estep_mode);
-    int32_t* mchg = momfreeze ? (int32_t*)(ws + c.mchg) : nullptr;
-    if ((rc = hip_rc(launch_em_init(pb.B, done, mchg, p->status,
-                                    debug_nondefault() ? SBCE_STATUS_DEBUG : 0,
-                                    small2 ? list_cnt : nullptr, s))))
-        return rc;
-
-    EstepArgs ea = estep_args(p, ws + c.mom, ws, &c);
-    ea.done = (early || cv || freeze) ? done : nullptr;
-    if (nz) {                                // the estimate starts at the caller's parameter
-        if ((rc = hip_rc(launch_noise_init(pb.B, nz->varn_est, p->varn_t, pb.varn, s)))) return rc;
-        ea.varn_t = nz->varn_est;
-    }
-    ea.lists_zeroed = small2 && list_cnt != nullptr;
-    MstepArgs ma = mstep_args(pb, p, ea.mom, ws, c, solve_mode);
-    ma.done = ea.done;
-    if (freeze) ma.freeze_w = done;
-    if (momfreeze) ma.mchg = mchg;
-
-    EstepArgs eas = ea;                      // superimposed pilots: E-step on y - H x_p
-    if (p->x_sup) eas.yd = (const cd*)(ws + c.ysh);
-    // the Kronecker factors of the pilot regressors do not change across iterations
-    const bool prefactor = rbuild_herm_supported(pb);
-    if (prefactor && (rc = hip_rc(launch_pilot_factor(pb, ma, s)))) return rc;
-    // the LLF kernel reads theta before the stop decision of the same iteration: no fold with it
-    // nor with the noise update, which follows a trial's last M-step
-    const bool fold_stop = small2 && early && !p->llf && !nz;
+    Carve c;
+    char* ws = nullptr;
+    int32_t* done = nullptr;
+    int32_t* list_cnt = nullptr;
+    int32_t* mchg = nullptr;
+    bool empty = true;                       // no trial or no iteration: nothing is issued
+    bool gauss = false, early = false, small = false, small2 = false, freeze = false,
+         momfreeze = false, prefactor = false, fold_stop = false;
+    EstepArgs ea, eas;
+    MstepArgs ma;
     ConvArgs ca{};
     LoglikArgs la{};
-    if (cv) {                                // theta_{-1} is the caller's h_initial
-        char* cs = (char*)cv->scratch;
-        double* ll_cur = (double*)(cs + conv_prev_bytes(pb));
-        ca.theta = ma.theta; ca.prev = (cd*)cs; ca.ll_cur = ll_cur;
-        ca.dth_hist = cv->dtheta_hist; ca.ll_hist = cv->ll_hist; ca.done = done;
-        ca.iters_done = p->iters_done; ca.status = p->status;
-        ca.tol_theta2 = cv->tol_theta * cv->tol_theta; ca.tol_ll = cv->tol_ll;
-        ca.min_iters = cv->min_iters; ca.iters = iters;
-        if (cv->ll_hist) {
-            la = loglik_args(pb, p, ll_cur, nullptr, cs + conv_prev_bytes(pb) + conv_ll_bytes(pb));
-            la.varn_t = ea.varn_t;           // the current parameter (the estimate, with nz)
-            la.done = done;
-        }
-        if ((rc = hip_rc(launch_conv_init(pb, ma.theta, ca.prev, s)))) return rc;
+    // the all-frozen report (MstepArgs::report and what em_init_kernel writes to its block), set
+    // before begin() by a paced sbce_em_multi problem; only with `freeze`
+    FreezeReport* rep = nullptr;
+    int32_t* rep_word = nullptr;
+    int32_t rep_gen = 0;
+
+    int check(const sbce_dims* d, const sbce_ptrs* p_, int iters_, int estep_mode_, int solve_mode_,
+              const sbce_noise_opts* nz_, const sbce_conv_opts* cv_, void* hip_stream) {
+        p = p_; nz = nz_; cv = cv_;
+        iters = iters_; estep_mode = estep_mode_; solve_mode = solve_mode_;
+        s = (hipStream_t)hip_stream;
+        if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
+        if ((nz || cv) && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
+        if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
+        if (!valid_solve(solve_mode)) return SBCE_EINVAL;
+        int rc = check_ptrs(p, pb, true, solve_mode);
+        if (rc) return rc;
+        if (p->llf && !p->x_d_true) return SBCE_EINVAL;
+        gauss = estep_mode == SBCE_ESTEP_GAUSS;
+        if (gauss && !(pb.varx > 0.0)) return SBCE_EINVAL;
+        const bool hard = estep_mode == SBCE_ESTEP_HARD || estep_mode == SBCE_ESTEP_ZF ||
+                          estep_mode == SBCE_ESTEP_MMSE;
+        if (p->x_dest && (!hard || !aligned16(p->x_dest))) return SBCE_EINVAL;
+        if (p->x_sup && ((estep_mode != SBCE_ESTEP_SOFT && estep_mode != SBCE_ESTEP_HARD) ||
+                         !aligned16(p->x_sup)))
+            return SBCE_EINVAL;
+        if (nz && (rc = check_noise(p, nz, pb))) return rc;
+        if (cv && (rc = check_conv(p, cv, pb))) return rc;
+        empty = pb.B == 0 || iters == 0;
+        c = carve(pb, solve_mode);
+        ws = (char*)p->workspace;
+        done = (int32_t*)(ws + c.done);
+        early = p->h_true != nullptr;
+        // L <= 64: the whole M-step in one launch (BASELINE cfg 5: L = 32)
+        small = mstep_small_supported(pb, solve_mode) && !(gauss && pb.NR == 1);
+        // n_tx <= 2 small path: its solve launch zeroes the E-step's list counters for the next
+        // iteration, em_init_kernel for the first -- no counter memset per E-step
+        small2 = small && mstep_small2_selected(pb);
+        list_cnt = c.has_prep ? (int32_t*)(ws + c.list) + (size_t)pb.B * pb.Td : nullptr;
+        // The fixed-point freeze: the plain chain is a pure function of theta
+        // per trial, so once the back substitution stores the theta it overwrites bit for bit, the
+        // trial's later iterations would repeat this one -- the back substitution flags the trial
+        // and the kernels skip it.  Armed only where theta is the whole state and nothing reads it
+        // per iteration: not with the noise estimate, the conv stop (it owns the flags), the oracle
+        // stop (iters_done counts executed iterations), the LLF history or superimposed pilots, and
+        // only on the batched-panel solve, whose back substitutions carry the fold.
+        freeze = !nz && !cv && !early && !p->llf && !p->x_sup && !small &&
+                 chol_batched_selected(pb, solve_mode);
+        // The moment-repeat rule: the M-step is a pure function of the moments
+        // and the call's constant inputs, so a trial whose E-step rewrote its moments bit for bit
+        // is at its fixed point one M-step before the theta compare sees it.  The moment stores of
+        // the E-step flag a change in mchg[b]; the M-step's launches skip a trial without one and
+        // the back substitution freezes it.  Armed with the freeze, and only where every moment
+        // writer of the launched E-step carries the fold.
+        momfreeze = freeze && estep_momfold_supported(pb, estep_mode);
+        mchg = momfreeze ? (int32_t*)(ws + c.mchg) : nullptr;
+        return SBCE_OK;
     }
-    for (int it = 0; it < iters; ++it) {
+
+    int begin() {
+        if (empty) return SBCE_OK;
+        int rc;
+        if ((rc = hip_rc(launch_em_init(pb.B, done, mchg, p->status,
+                                        debug_nondefault() ? SBCE_STATUS_DEBUG : 0,
+                                        small2 ? list_cnt : nullptr, s, freeze ? rep : nullptr, rep_gen,
+                                        rep_word))))
+            return rc;
+
+        ea = estep_args(p, ws + c.mom, ws, &c);
+        ea.done = (early || cv || freeze) ? done : nullptr;
+        if (nz) {                            // the estimate starts at the caller's parameter
+            if ((rc = hip_rc(launch_noise_init(pb.B, nz->varn_est, p->varn_t, pb.varn, s))))
+                return rc;
+            ea.varn_t = nz->varn_est;
+        }
+        ea.lists_zeroed = small2 && list_cnt != nullptr;
+        ma = mstep_args(pb, p, ea.mom, ws, c, solve_mode);
+        ma.done = ea.done;
+        if (freeze) ma.freeze_w = done;
+        if (momfreeze) ma.mchg = mchg;
+        if (freeze) ma.report = rep;
+
+        eas = ea;                            // superimposed pilots: E-step on y - H x_p
+        if (p->x_sup) eas.yd = (const cd*)(ws + c.ysh);
+        // the Kronecker factors of the pilot regressors do not change across iterations
+        prefactor = rbuild_herm_supported(pb);
+        if (prefactor && (rc = hip_rc(launch_pilot_factor(pb, ma, s)))) return rc;
+        // the LLF kernel reads theta before the stop decision of the same iteration: no fold with
+        // it nor with the noise update, which follows a trial's last M-step
+        fold_stop = small2 && early && !p->llf && !nz;
+        if (cv) {                            // theta_{-1} is the caller's h_initial
+            char* cs = (char*)cv->scratch;
+            double* ll_cur = (double*)(cs + conv_prev_bytes(pb));
+            ca.theta = ma.theta; ca.prev = (cd*)cs; ca.ll_cur = ll_cur;
+            ca.dth_hist = cv->dtheta_hist; ca.ll_hist = cv->ll_hist; ca.done = done;
+            ca.iters_done = p->iters_done; ca.status = p->status;
+            ca.tol_theta2 = cv->tol_theta * cv->tol_theta; ca.tol_ll = cv->tol_ll;
+            ca.min_iters = cv->min_iters; ca.iters = iters;
+            if (cv->ll_hist) {
+                la = loglik_args(pb, p, ll_cur, nullptr, cs + conv_prev_bytes(pb) + conv_ll_bytes(pb));
+                la.varn_t = ea.varn_t;       // the current parameter (the estimate, with nz)
+                la.done = done;
+            }
+            if ((rc = hip_rc(launch_conv_init(pb, ma.theta, ca.prev, s)))) return rc;
+        }
+        return SBCE_OK;
+    }
+
+    int iteration(int it) {
+        if (empty) return SBCE_OK;
+        int rc;
         if (p->x_sup) {
             if ((rc = hip_rc(launch_sup_shift_y(pb, ea.yd, ea.psid, ea.theta, (const cd*)p->x_sup,
                                                 (cd*)(ws + c.ysh), ea.done, s))))
@@ -498,16 +543,153 @@ static int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
             ca.it = it;
             if ((rc = hip_rc(launch_conv_step(pb, ca, s)))) return rc;
         }
+        return SBCE_OK;
     }
-    if (p->x_dest && (rc = hip_rc(launch_decisions(pb, ea.mom, (cd*)p->x_dest, s)))) return rc;
-    if (!early && !cv && p->iters_done) {
-        // every trial ran all iterations: fill with `iters` via a tiny host-free memset pattern
-        // (int32 fill is done on device by hipMemsetD32Async)
-        if (hipMemsetD32Async((hipDeviceptr_t)p->iters_done, iters, (size_t)pb.B, s) != hipSuccess)
-            return SBCE_EHIP;
+
+    int finish() {
+        if (empty) return SBCE_OK;
+        int rc;
+        if (p->x_dest && (rc = hip_rc(launch_decisions(pb, ea.mom, (cd*)p->x_dest, s)))) return rc;
+        if (!early && !cv && p->iters_done) {
+            // every trial ran all iterations: fill with `iters` via a tiny host-free memset pattern
+            // (int32 fill is done on device by hipMemsetD32Async)
+            if (hipMemsetD32Async((hipDeviceptr_t)p->iters_done, iters, (size_t)pb.B, s) != hipSuccess)
+                return SBCE_EHIP;
+        }
+        return SBCE_OK;
     }
+};
+
+int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+           const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream) {
+    clear_stale_error();
+    EmChain ch;
+    int rc = ch.check(d, p, iters, estep_mode, solve_mode, nz, cv, hip_stream);
+    if (rc) return rc;
+    if ((rc = ch.begin())) return rc;
+    for (int it = 0; it < iters; ++it)
+        if ((rc = ch.iteration(it))) return rc;
+    return ch.finish();
+}
+
+// ---- sbce_em_multi's pacing: what a paced problem needs from the library, pooled.
+// A slot holds one int32 of pinned, host-mapped, coherent memory (the word the device stores the
+// call's generation to), the device counter of frozen trials and the events of the iterations in
+// flight.  Slots are made on first need, kept for the life of the process and handed out under a
+// mutex: a steady-state call allocates nothing.  The word is never reset: every call compares
+// with a generation of its own, so what an earlier call stored compares unequal.
+constexpr int kMultiMax = 8;
+#ifndef SBCE_EM_LEAD_DEFAULT
+#define SBCE_EM_LEAD_DEFAULT 2
+#endif
+// The default lead and the wait (0: hipEventSynchronize on blocking-sync events, 1: a spin on
+// hipEventQuery) were chosen by measurement at cfg1 (profiles/emstop/README.md: leads 1 / 2 / 3
+// and both waits as arms built with these macros); the two waits do not differ there, and the
+// blocking one leaves the host core free.
+#ifndef SBCE_EM_WAIT_SPIN
+#define SBCE_EM_WAIT_SPIN 0
+#endif
+
+struct PaceSlot {
+    int device = -1;
+    bool busy = false;
+    int32_t* word = nullptr;       // host address
+    int32_t* word_dev = nullptr;   // the same word as the device sees it
+    FreezeReport* rep = nullptr;   // device memory: the counter, the generation, the word's address
+    std::vector<hipEvent_t> ev;    // ring of `lead` events, grown to the largest lead seen
+    hipEvent_t tail = nullptr;     // end of the last call that used the slot
+    hipStream_t last = nullptr;    // ... and its stream
+    bool used = false;
+};
+
+std::mutex g_pace_mu;
+std::vector<PaceSlot*> g_pace;
+std::atomic<uint32_t> g_pace_gen{0};
+
+constexpr unsigned kPaceEventFlags =
+    hipEventDisableTiming | (SBCE_EM_WAIT_SPIN ? 0u : (unsigned)hipEventBlockingSync);
+
+void pace_release(PaceSlot* sl) {
+    std::lock_guard<std::mutex> lk(g_pace_mu);
+    sl->busy = false;
+}
+
+// A free slot of `device` with at least `nev` events, preferring the one this stream used last
+// (its counter and word are then ordered by the stream itself).  A slot last used on another
+// stream may still have that call's tail in flight: the new stream waits for its end first, so
+// the counter is never zeroed under a late increment.
+int pace_acquire(int device, hipStream_t s, int nev, PaceSlot** out) {
+    PaceSlot* sl = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_pace_mu);
+        for (PaceSlot* q : g_pace) {
+            if (q->busy || q->device != device) continue;
+            if (!sl || (q->used && q->last == s)) sl = q;
+            if (sl->used && sl->last == s) break;
+        }
+        if (!sl) {
+            sl = new PaceSlot;
+            sl->device = device;
+            g_pace.push_back(sl);
+        }
+        sl->busy = true;
+    }
+    // each resource is made where it is still missing, so a slot whose first set-up failed half
+    // way is completed by the next call instead of being used half-built
+    bool ok = true;
+    if (!sl->word) {
+        void* h = nullptr;
+        ok = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+        if (ok) {
+            sl->word = (int32_t*)h;
+            *sl->word = 0;
+        }
+    }
+    if (ok && !sl->word_dev) {
+        void* dv = nullptr;
+        ok = hipHostGetDevicePointer(&dv, sl->word, 0) == hipSuccess && dv;
+        if (ok) sl->word_dev = (int32_t*)dv;
+    }
+    if (ok && !sl->rep) {
+        void* r = nullptr;
+        ok = hipMalloc(&r, sizeof(FreezeReport)) == hipSuccess && r;
+        if (ok) sl->rep = (FreezeReport*)r;
+    }
+    if (ok && !sl->tail) {
+        hipEvent_t e = nullptr;
+        ok = hipEventCreateWithFlags(&e, kPaceEventFlags) == hipSuccess;
+        if (ok) sl->tail = e;
+    }
+    while (ok && (int)sl->ev.size() < nev) {
+        hipEvent_t e;
+        ok = hipEventCreateWithFlags(&e, kPaceEventFlags) == hipSuccess;
+        if (ok) sl->ev.push_back(e);
+    }
+    if (ok && sl->used && sl->last != s) ok = hipStreamWaitEvent(s, sl->tail, 0) == hipSuccess;
+    if (!ok) {
+        pace_release(sl);
+        return SBCE_EHIP;
+    }
+    *out = sl;
     return SBCE_OK;
 }
+
+// The host waits only for work that is already enqueued, never for the word itself.
+int pace_wait(hipEvent_t e) {
+#if SBCE_EM_WAIT_SPIN
+    hipError_t r;
+    while ((r = hipEventQuery(e)) == hipErrorNotReady) {
+    }
+    (void)hipGetLastError();                 // "not ready" is no error of this call's launches
+    return hip_rc(r);
+#else
+    return hip_rc(hipEventSynchronize(e));
+#endif
+}
+
+}  // namespace
+
+extern "C" {
 
 int sbce_em(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
             void* hip_stream) {
@@ -518,6 +700,78 @@ int sbce_em_noise(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
                   const sbce_noise_opts* o, void* hip_stream) {
     if (!o) return SBCE_EINVAL;
     return em_run(d, p, iters, estep_mode, solve_mode, o, nullptr, hip_stream);
+}
+
+int sbce_em_multi(int n, const sbce_dims* const* dims, const sbce_ptrs* const* ptrs, int iters,
+                  int estep_mode, int solve_mode, void* const* hip_streams, int lead,
+                  int* iters_issued) {
+    if (n < 1 || n > kMultiMax || !dims || !ptrs || !hip_streams) return SBCE_EINVAL;
+    if (lead < 0 || (lead > 0 && lead > iters)) return SBCE_EINVAL;
+    EmChain ch[kMultiMax];
+    for (int j = 0; j < n; ++j) {            // every argument, before any HIP call
+        const int rc = ch[j].check(dims[j], ptrs[j], iters, estep_mode, solve_mode, nullptr, nullptr,
+                                   hip_streams[j]);
+        if (rc) return rc;
+    }
+    if (lead == 0) lead = SBCE_EM_LEAD_DEFAULT < iters ? SBCE_EM_LEAD_DEFAULT : iters;
+    clear_stale_error();
+    PaceSlot* slot[kMultiMax] = {};
+    int issued[kMultiMax] = {};
+    bool ended[kMultiMax] = {};
+    int rc = SBCE_OK;
+    // a problem is paced where its freeze is armed and its stream is not capturing (a capture
+    // records the whole fixed launch sequence; an event wait has no place in it)
+    int device = 0;
+    for (int j = 0; j < n && !rc; ++j) {
+        EmChain& c = ch[j];
+        if (!c.freeze || c.empty || lead >= iters) continue;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(c.s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            (void)hipGetLastError();
+            continue;
+        }
+        if (hipGetDevice(&device) != hipSuccess) { rc = SBCE_EHIP; break; }
+        if ((rc = pace_acquire(device, c.s, lead, &slot[j]))) break;
+        uint32_t g = ++g_pace_gen;
+        if (g == 0) g = ++g_pace_gen;        // the generation is never zero
+        c.rep = slot[j]->rep;
+        c.rep_word = slot[j]->word_dev;
+        c.rep_gen = (int32_t)g;
+    }
+    for (int j = 0; j < n && !rc; ++j) rc = ch[j].begin();
+    for (int it = 0; it < iters && !rc; ++it) {
+        for (int j = 0; j < n && !rc; ++j) {
+            if (ended[j]) continue;
+            PaceSlot* sl = slot[j];
+            if (sl && it >= lead) {
+                // iteration it - lead is complete: if it (or an earlier one) froze the last live
+                // trial, the word holds this call's generation and every later iteration is the
+                // identity -- none is issued
+                if ((rc = pace_wait(sl->ev[it % lead]))) break;
+                if (__atomic_load_n(sl->word, __ATOMIC_ACQUIRE) == ch[j].rep_gen) {
+                    ended[j] = true;
+                    continue;
+                }
+            }
+            if ((rc = ch[j].iteration(it))) break;
+            if (!ch[j].empty) ++issued[j];
+            if (sl && it + lead < iters) rc = hip_rc(hipEventRecord(sl->ev[it % lead], ch[j].s));
+        }
+    }
+    for (int j = 0; j < n; ++j) {
+        if (!rc) rc = ch[j].finish();
+        if (slot[j]) {
+            if (hipEventRecord(slot[j]->tail, ch[j].s) == hipSuccess) {
+                slot[j]->last = ch[j].s;
+                slot[j]->used = true;
+            } else if (!rc) {
+                rc = SBCE_EHIP;
+            }
+            pace_release(slot[j]);
+        }
+        if (iters_issued) iters_issued[j] = issued[j];
+    }
+    return rc;
 }
 
 int sbce_conv_workspace_bytes(const sbce_dims* d, int want_ll, size_t* bytes) {

@@ -1401,11 +1401,25 @@ void panel_factor_kernel(MstepArgs a, int L, int NR, int jb, int ntile, int skip
 #if SBCE_AB
 __device__ unsigned long long g_mom_skip;      // trial-M-steps skipped (sbce_debug_momskip)
 #endif
+// The one lane that freezes trial b (a trial goes 0 -> 1 once per call: a flagged trial returns
+// before every site).  All-frozen report (armed by a.report, sbce_em_multi's paced problems):
+// the lane counts the trial, and the one that counts the last trial of the batch publishes the
+// call's generation to the host.  An integer count: no result depends on the order.
+__device__ __forceinline__ void freeze_trial(const MstepArgs& a, int b) {
+    a.freeze_w[b] = 1;
+    if (a.report && atomicAdd(&a.report->frozen_cnt, 1) + 1 == a.nbatch) {
+        const int32_t gen = a.report->gen;
+        int32_t* word = a.report->all_frozen;
+        __threadfence_system();
+        __hip_atomic_store(word, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 __device__ __forceinline__ bool backsub_skip(const MstepArgs& a, int b, int tid) {
     if (a.done && a.done[b]) return true;
     if (!(a.mskip && !a.mskip[b])) return false;
     if (tid == 0) {
-        a.freeze_w[b] = 1;
+        freeze_trial(a, b);
 #if SBCE_AB
         atomicAdd(&g_mom_skip, 1ull);
 #endif
@@ -1448,7 +1462,7 @@ __global__ __launch_bounds__(256) void backsub_kernel(MstepArgs a, int L, int NR
             diff |= theta_bits_differ(old, x);
             th[e] = x;
         }
-        if (!__syncthreads_or(diff != 0) && tid == 0) a.freeze_w[b] = 1;
+        if (!__syncthreads_or(diff != 0) && tid == 0) freeze_trial(a, b);
         return;
     }
     for (int e = tid; e < L * NR; e += nth) th[e] = cconj(y[e]);
@@ -1720,7 +1734,7 @@ void backsub4_kernel(MstepArgs a, int L) {
         __syncthreads();
     }
     // no entry of theta changed a bit: every later iteration of this trial would repeat this one
-    if (arm && wave == 0 && __ballot(diff != 0) == 0 && lane == 0) a.freeze_w[b] = 1;
+    if (arm && wave == 0 && __ballot(diff != 0) == 0 && lane == 0) freeze_trial(a, b);
 }
 
 // DIAGNOSTIC launch timing (sbce_debug_chol_timing): HIP events around the wide schedule's

@@ -623,7 +623,8 @@ hipError_t launch_llf(const Problem& pb, const cd* theta, const cd* yp, const cd
 
 namespace {
 __global__ __launch_bounds__(256) void em_init_kernel(int B, int32_t* done, int32_t* mchg, int32_t* status,
-                                                      int sv, int32_t* cnt) {
+                                                      int sv, int32_t* cnt, FreezeReport* rep, int32_t gen,
+                                                      int32_t* word) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < B) {
         done[i] = 0;
@@ -631,13 +632,18 @@ __global__ __launch_bounds__(256) void em_init_kernel(int B, int32_t* done, int3
         if (status) status[i] = sv;
     }
     if (cnt && i < 5) cnt[i] = 0;
+    if (rep && i == 0) {
+        rep->frozen_cnt = 0;
+        rep->gen = gen;
+        rep->all_frozen = word;
+    }
 }
 }  // namespace
 
 hipError_t launch_em_init(int B, int32_t* done, int32_t* mchg, int32_t* status, int sv, int32_t* cnt,
-                          hipStream_t s) {
+                          hipStream_t s, FreezeReport* rep, int32_t gen, int32_t* word) {
     hipLaunchKernelGGL(em_init_kernel, dim3((B + 255) / 256 > 0 ? (B + 255) / 256 : 1), dim3(256), 0,
-                       s, B, done, mchg, status, sv, cnt);
+                       s, B, done, mchg, status, sv, cnt, rep, gen, word);
     return hipGetLastError();
 }
 

@@ -412,6 +412,14 @@ inline bool gauss_products(int solve_mode) {
                              solve_mode == kSolveClampHpd);
 }
 
+// The all-frozen report's block (library-owned device memory, written by em_init_kernel at the
+// start of every paced call)
+struct FreezeReport {
+    int32_t frozen_cnt;    // trials frozen so far in this call
+    int32_t gen;           // the call's generation, non-zero
+    int32_t* all_frozen;   // one int32 of host-mapped pinned memory (its device address)
+};
+
 struct MstepArgs {
     const cd* yd;
     const cd* yp;      // [B][Tp][NR]
@@ -465,6 +473,12 @@ struct MstepArgs {
     // compared nothing: every trial changed).
     int32_t* mchg = nullptr;         // [B]
     const int32_t* mskip = nullptr;  // [B]
+    // the all-frozen report of a paced sbce_em_multi problem (armed with freeze_w; null: not
+    // armed): the lane that sets freeze_w[b] also counts the trial in report->frozen_cnt, and the
+    // one that counts the nbatch-th stores the call's generation to the host-mapped word -- the
+    // host then ends the launch sequence.  One pointer to a block in device memory, so that the
+    // kernels carry two more scalar registers, not five, and read the rest only in the rare branch
+    FreezeReport* report = nullptr;
 };
 
 // block-uniform, at the head of every M-step kernel of the batched-panel chain: the trial has
@@ -558,10 +572,11 @@ hipError_t launch_nmse(const Problem& pb, const cd* theta, const cd* h, double* 
 hipError_t launch_llf(const Problem& pb, const cd* theta, const cd* yp, const cd* up,
                       const cd* yd, const cd* psid, const cd* xd, double* llf, int iters,
                       int it, const int32_t* done, const double* varn_t, hipStream_t s);
-// sbce_em's start in one launch: done[b] = 0, (mchg) mchg[b] = 0, status[b] = status_value, and
-// (cnt) 5 counters = 0
+// sbce_em's start in one launch: done[b] = 0, (mchg) mchg[b] = 0, status[b] = status_value,
+// (cnt) 5 counters = 0 and (rep) the all-frozen report's block = {0, gen, word}
 hipError_t launch_em_init(int B, int32_t* done, int32_t* mchg, int32_t* status, int status_value, int32_t* cnt,
-                          hipStream_t s);
+                          hipStream_t s, FreezeReport* rep = nullptr, int32_t gen = 0,
+                          int32_t* word = nullptr);
 hipError_t launch_early_stop(const Problem& pb, const cd* theta, const cd* h,
                              int32_t* done, int32_t* iters_done, int it, hipStream_t s);
 

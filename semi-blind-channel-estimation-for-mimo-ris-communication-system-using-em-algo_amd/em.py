@@ -1043,8 +1043,11 @@ class EMEngine:
     issues ONE sbce_em call on the current stream.  Nothing is allocated or
     synchronised inside ``run()``.
 
-    ``streams = K > 1``: ``run()`` issues the batch as K contiguous sub-batches, one sbce_em
-    call each on its own HIP stream (forked from and joined back into the current stream).
+    ``streams = K > 1``: ``run()`` issues the batch as K contiguous sub-batches, each on its own HIP
+    stream (forked from and joined back into the current stream), through ONE sbce_em_multi call:
+    where the fixed-point rule is armed the launch sequence of a sub-batch ends once all its
+    trials are frozen, so run() may wait for the device (include/sbce.h); ``iters_issued`` holds
+    the iterations the last run() enqueued per sub-batch.
     Trials are independent and every kernel treats them independently, so theta is bitwise
     the same; the sub-batches' kernels overlap -- the latency-bound launches of one (the
     Cholesky panel factors, the enumeration tail) run beside the MFMA-bound ones of another.
@@ -1107,6 +1110,15 @@ class EMEngine:
                 off += nb
                 ptrs = st.ptrs(slice(int(b0), int(b1)), ws=ws, h_true=hp)
                 self.subs.append((dims, ptrs, ws, torch.cuda.Stream()))
+            # sbce_em_multi's argument arrays over the sub-batches
+            n = len(self.subs)
+            self._multi = (
+                (ctypes.POINTER(_lib.Dims) * n)(*[ctypes.pointer(s[0]) for s in self.subs]),
+                (ctypes.POINTER(_lib.Ptrs) * n)(*[ctypes.pointer(s[1]) for s in self.subs]),
+                (ctypes.c_void_p * n)(*[s[3].cuda_stream for s in self.subs]),
+                (ctypes.c_int * n)())
+        # iterations the last run() enqueued per sub-batch (empty without sub-batches)
+        self.iters_issued = []
 
     def run(self, itera, stream=None):
         """One full EM (itera iterations) over the whole batch, stream-ordered on `stream`
@@ -1123,10 +1135,12 @@ class EMEngine:
             return self.theta
         ev = self.torch.cuda.Event()
         ev.record(cur)
-        for dims, ptrs, _, st in self.subs:
+        for _, _, _, st in self.subs:
             st.wait_event(ev)
-            _lib.check(self.lib.sbce_em(dims, ptrs, int(itera), self.mode, self.solve, st.cuda_stream),
-                       "sbce_em")
+        dims, ptrs, streams, issued = self._multi
+        _lib.check(self.lib.sbce_em_multi(len(self.subs), dims, ptrs, int(itera), self.mode,
+                                          self.solve, streams, 0, issued), "sbce_em_multi")
+        self.iters_issued = list(issued)
         for _, _, _, st in self.subs:
             cur.wait_stream(st)
         return self.theta
