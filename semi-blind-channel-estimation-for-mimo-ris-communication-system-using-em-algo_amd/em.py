@@ -957,8 +957,10 @@ def em_zero_init(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, v
 
 # ------------------------------------------------------------------ diagnostic stages
 def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0, varx=1.0,
-                workspace=True):
-    """One device E-step (sbce_estep): returns m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx).
+                workspace=True, return_status=False):
+    """One device E-step (sbce_estep): returns m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx) and, with
+    return_status, the (B,) status words (SBCE_STATUS_DETECTOR: a ZF / MMSE decision past the
+    hypothesis table).  varn may be one value or one per trial ((B,), as em_batch takes it).
     workspace=False passes no workspace (the exact sweep then prepares each symbol in
     its own kernel instead of the separate preparation pass)."""
     torch = _torch()
@@ -968,14 +970,15 @@ def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0,
     y_p = np.zeros((B, 0, n_rx), dtype=complex)
     u_p = np.zeros((B, 0, P * n_tx), dtype=complex)
     st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta, varn, partition_r, varx,
-                 workspace=workspace)
+                 check="theta" if np.ndim(varn) else None, workspace=workspace)
     mom = torch.zeros((B, T_d, n_tx + n_tx * n_tx), dtype=torch.complex128, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     _lib.check(lib.sbce_estep(st.dims, st.ptrs(), _MODES[mode], mom.data_ptr(), stream),
                "sbce_estep")
     torch.cuda.current_stream().synchronize()
     mom = mom.cpu().numpy()
-    return mom[..., :n_tx], mom[..., n_tx:].reshape(B, T_d, n_tx, n_tx)
+    out = mom[..., :n_tx], mom[..., n_tx:].reshape(B, T_d, n_tx, n_tx)
+    return (*out, st.status.cpu().numpy()) if return_status else out
 
 
 def mstep_batch(y_d, y_p, psi_d, u_p, cons, m, S, varn, solve="chol", return_tol=False,

@@ -37,6 +37,12 @@ def _qam16_perm():
     return qam(16)[np.random.default_rng(1234).permutation(16)]
 
 
+def _qam64_perm():
+    # this draw puts 1 + 1j first of the four innermost points: at z = 0 the first minimum in table
+    # order is then not the point lowest on both axes, which a per-axis search meets first
+    return qam(64)[np.random.default_rng(4324).permutation(64)]
+
+
 def _qam16_uneven():
     re = np.array([-3.0, -1.0, 1.5, 4.0])
     im = np.array([-2.5, -1.0, 0.5, 3.0])
@@ -59,6 +65,7 @@ TABLES = {
     "qam16": lambda: qam(16),
     "qam64": lambda: qam(64),
     "qam16_perm": _qam16_perm,                       # a grid (K = 4), permuted table order
+    "qam64_perm": _qam64_perm,                       # a grid (K = 8), permuted table order
     "qam16_uneven": _qam16_uneven,                   # a grid (K = 4), unequal spacing, off centre
     "qam16_rot": lambda: qam(16) * np.exp(0.3j),     # no grid (K = 0)
     "psk8": lambda: psk(8),

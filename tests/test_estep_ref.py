@@ -42,10 +42,10 @@ def test_chunking_does_not_change_the_result():
 
 def test_tables_and_grid_classes():
     """The class grid_build puts each table in: K > 0 (a level grid in any order) or 0."""
-    want = {"qam16": 4, "qam64": 8, "qam16_perm": 4, "qam16_uneven": 4, "qam16_rot": 0,
-            "psk8": 0, "psk16": 0, "bpsk": 0, "cross32": 0, "apsk64": 0}
-    size = {"qam16": 16, "qam64": 64, "qam16_perm": 16, "qam16_uneven": 16, "qam16_rot": 16,
-            "psk8": 8, "psk16": 16, "bpsk": 2, "cross32": 32, "apsk64": 64}
+    want = {"qam16": 4, "qam64": 8, "qam16_perm": 4, "qam64_perm": 8, "qam16_uneven": 4,
+            "qam16_rot": 0, "psk8": 0, "psk16": 0, "bpsk": 0, "cross32": 0, "apsk64": 0}
+    size = {"qam16": 16, "qam64": 64, "qam16_perm": 16, "qam64_perm": 64, "qam16_uneven": 16,
+            "qam16_rot": 16, "psk8": 8, "psk16": 16, "bpsk": 2, "cross32": 32, "apsk64": 64}
     assert set(want) == set(er.TABLES)
     for name, K in want.items():
         c = er.table(name)
