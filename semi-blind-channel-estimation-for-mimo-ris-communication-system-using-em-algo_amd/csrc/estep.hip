@@ -516,10 +516,14 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // 2 x staged record (DMA double buffer: 128 + 32 done words, or the record itself) |
 // FP32 screen tables (V16: alpha and U as floats, kScreenD doubles)
 constexpr int mfma_rec_d(int rec_words) { return 2 * (rec_words <= 128 ? 160 : (rec_words + 1) / 2 * 2 + 32); }
+// ... | per-group bound tables (V16, i.e. M = 16 with a 256-row chunk: U', V', Q' as floats,
+// 64 steps each, then 256 floats that hold the projected vectors and after them alpha')
+constexpr int mfma_tri_d(int steps) { return 3 * 64 * steps / 2 + 128; }
 constexpr int mfma_tab_d(int NO, int chunk, int steps, int M, int nkt_pad, int rec_words) {
     return (2 * NO + chunk + 3 * (4 * steps) * M + nkt_pad + 128 + 1) / 2 * 2 + mfma_rec_d(rec_words) +
-           kScreenD;
+           kScreenD + (M == 16 && chunk == 256 ? mfma_tri_d(steps) : 0);
 }
+constexpr int kTriGate = 4;     // tile groups of a symbol at the screen before its bound tables are built
 
 struct MfmaConst {
     int B, Td, P, M, lm;
@@ -536,6 +540,8 @@ struct MfmaConst {
     int rec_words;             // prep record + y_t, doubles (staged per symbol in LDS)
     int spw;                   // symbols per wave (consecutive; the next record prefetched)
     int screen;                // V16 FP32 screen of the tile groups (SBCE_ESTEP_F32=0 disables)
+    int tri;                   // V16 per-group bounds T_3 / T_1 (SBCE_ESTEP_TRI: 0 off, 1 built once
+                               // kTriGate groups of the symbol reached the screen, 2 always built)
 };
 
 // V16 (M == 16, NA == 2): the A operand's V term, V[kk][i & 15] = V[kk][lane & 15], is the
@@ -637,6 +643,9 @@ __device__ double column_tile_bounds(const cd* H, const cd* yg, const cd* s_cons
 // Diagnostic (MfmaConst::count, SBCE_ESTEP_COUNT=1): FP64 MFMAs the sweep issued, for the
 // executed-work roofline next to the bounds' pruning.
 __device__ unsigned long long g_estep_mfma;
+// ... and the V16 tile groups that survived every bound and reached the FP32 screen (the FP64
+// test with the screen off): what the bounds leave the screen to reject.
+__device__ unsigned long long g_estep_groups;
 
 template <int NT, int NR, int MODE, int TU, bool V16>
 __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaConst& c) {
@@ -939,8 +948,143 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     bool scr_on = V16 && c.screen;   // wave-uniform
     int scr_n = 0, scr_pass = 0;
 
+    // Per-group bounds (V16).  The column-tile and row-tile bounds above each relax TWO streams
+    // to the continuum; at theta_0's ill-conditioned H_eff that is loose and most tile groups
+    // reach the screen only to be rejected there.  Relaxing ONE stream q (P_q = I - h_q h_q^H /
+    // ||h_q||^2, so P_q h_q = 0 and ||P_q v|| <= ||v||) bounds every hypothesis of the tile group
+    // G(kt, tg) (x_2 = cons[kt], x_0 in cons[tg .. tg+3], every x_1 and x_3) from below by
+    //   T_3 = min over x_0 in the block and x_1 of ||P_3 (y - h_0 x_0 - h_1 x_1 - h_2 x_2)||^2
+    //   T_1 = min over x_0 in the block and x_3 of ||P_1 (y - h_0 x_0 - h_3 x_3 - h_2 x_2)||^2.
+    // Each has the sweep's own form alpha'_i + gamma'_k - 2 Re p'_i^H q'_k with 256 rows
+    // (x_0, x_o), o = 1 or 3 (A operand U'_{x_0} + V'_{x_o}) and 16 columns x_2: per bound 16
+    // tiles of STEPS FP32 MFMAs and STEPS more for alpha', reduced to the 4 x 16 group table by an
+    // element-wise minimum over the four tiles of an x_0 block, the four rows of the lane and two
+    // cross-lane steps.  Lane (rq, col) keeps the bound of group (tg = 4 rq, kt = col):
+    // max(T_3, T_1), each less its rounding margin
+    //   2^-16 (2 A' + gamma'_kt) + 1e-9 S,   A' = 2 (max ||P(y - h_0 x)||^2 + max ||P h_o x||^2)
+    //   >= max alpha',   S = 4 (||y||^2 + max |x|^2 sum_a ||h_a||^2), of the order of the largest
+    //   distance (five terms: 5/4 S bounds every one; S only scales the 1e-9 term):
+    // the first term is the screen's 2^-17 (2 max alpha + gamma) (operands and alpha' rounded to
+    // FP32, K2 + 1 FP32 sums) doubled for alpha' being formed in FP32 as well, the second covers
+    // the FP64 projection (P_q h_q = 0 only to rounding) and the sweep's own FP64 rounding, as
+    // lb_margin does for the column bounds.  A group whose bound exceeds the skip bound holds no
+    // hypothesis the FP64 test would keep, so skipping it leaves every result bit as it was.
+    // ||h_q||^2 = 0, a column below 1e-20 of the largest, or a scale outside FP32's range leave
+    // that bound at 0, which skips nothing.  The projected vectors are formed here from H and y
+    // (the prep record has no room for them).
+    double tri_lane = 0.0;
+    bool tri_have = false;           // wave-uniform: the group table of this symbol is built
+    auto build_tri = [&]() {
+        float* tU = s_U32 + 256;
+        float* tV = tU + 64 * STEPS;
+        float* tQ = tV + 64 * STEPS;
+        float* tA = tQ + 64 * STEPS;                        // alpha', after the projected vectors
+        cd* pv = reinterpret_cast<cd*>(tA);                 // [4][8]: P y, P h_0, P h_o, P h_2
+        const int r = lane & 7, vi = (lane >> 3) & 3;
+        const bool own = r < NR;
+        const cd* yv = prep ? reinterpret_cast<const cd*>(s_rec + k_prep_stride)
+                            : a.yd + (size_t)gsym * NR;
+        const int xa4 = (lane ^ 4) << 2, xa2 = (lane ^ 2) << 2, xa1 = (lane ^ 1) << 2;
+        auto rsum = [&](double v) {                         // sum over the 8-lane group
+            v += bperm_d(v, xa4);
+            v += bperm_d(v, xa2);
+            return v + bperm_d(v, xa1);
+        };
+        const double cmax2 = wave_max_dpp(cabs2(s_cons[col]));
+        double hh = 0.0;                                    // ||h_a||^2 of the lane's column a = vi
+        hh = rsum(own ? cabs2(H[vi * NR + r]) : 0.0);
+        const double hmax = wave_max_dpp(hh);
+        const double hsum = (lane_d(hh, 0) + lane_d(hh, 8)) + (lane_d(hh, 16) + lane_d(hh, 24));
+        const double y2 = lane_d(rsum(own ? cabs2(yv[r]) : 0.0), 0);
+        const double S = 4.0 * fma(cmax2, hsum, y2);
+        const bool range_ok = S > 1e-30 && S < 1e30;
+#pragma unroll 1
+        for (int pass = 0; pass < 2; ++pass) {
+            const int q = pass ? 1 : 3, o = pass ? 3 : 1;
+            const cd hq = own ? H[q * NR + r] : czero();
+            const cd v = own ? (vi == 0 ? yv[r] : H[(vi == 1 ? 0 : (vi == 2 ? o : 2)) * NR + r]) : czero();
+            const double hq2 = rsum(cabs2(hq));
+            const bool ok = range_ok && hq2 > 0.0 && hq2 >= 1e-20 * hmax;
+            if (!__all(ok)) continue;
+            const cd cf = cscale(cmk(rsum(fma(hq.x, v.x, hq.y * v.y)), rsum(fma(hq.x, v.y, -hq.y * v.x))),
+                                 1.0 / hq2);               // h_q^H v / ||h_q||^2
+            const cd pvv = csub(v, cmul(hq, cf));
+            wave_sync();                                    // the other pass has read alpha'
+            if (lane < 32) pv[vi * 8 + r] = own ? pvv : czero();
+            wave_sync();
+            double uu = 0.0, vv = 0.0, qq = 0.0;
+#pragma unroll
+            for (int it = 0; it < STEPS; ++it) {
+                const int kk = 4 * it + rq, e = kk * 16 + col;
+                double u = 0.0, w = 0.0, q2 = 0.0;
+                if (kk < K2) {
+                    const int rr = kk >> 1;
+                    const cd x = s_cons[col];
+                    const cd pu = csub(pv[rr], cmul(pv[8 + rr], x));
+                    const cd hv = cmul(pv[16 + rr], x);
+                    const cd hx = cmul(pv[24 + rr], x);
+                    u = -2.0 * ((kk & 1) ? pu.y : pu.x);
+                    w = 2.0 * ((kk & 1) ? hv.y : hv.x);
+                    q2 = (kk & 1) ? hx.y : hx.x;
+                }
+                tU[e] = (float)u;
+                tV[e] = (float)w;
+                tQ[e] = (float)q2;
+                uu = fma(u, u, uu);
+                vv = fma(w, w, vv);
+                qq = fma(q2, q2, qq);
+            }
+            // |U'_x|^2, |V'_x|^2 and gamma'_x = ||q'_x||^2 of x = cons[col], in every lane of the column
+            uu += bperm_d(uu, xaddr16); uu += bperm_d(uu, xaddr32);
+            vv += bperm_d(vv, xaddr16); vv += bperm_d(vv, xaddr32);
+            qq += bperm_d(qq, xaddr16); qq += bperm_d(qq, xaddr32);
+            const double amaxp = 0.5 * (wave_max_dpp(uu) + wave_max_dpp(vv));
+            const double margin = fma(0x1p-16, 2.0 * amaxp + qq, 1e-9 * S);
+            wave_sync();                                    // tables written, pv read
+            // alpha'[s0][s1] = 0.25 (|U'_s0|^2 + |V'_s1|^2) + 0.5 U'_s0 . V'_s1, the cross terms
+            // by STEPS MFMAs: this lane's values are rows s0 = 4 rq + j, column s1 = col
+            float vr32[STEPS], qr32[STEPS];
+            f4v cx = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                vr32[s] = tV[(4 * s + rq) * 16 + col];
+                qr32[s] = tQ[(4 * s + rq) * 16 + col];
+                cx = __builtin_amdgcn_mfma_f32_16x16x4f32(tU[(4 * s + rq) * 16 + col], vr32[s], cx, 0, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double us = bperm_d(uu, (4 * rq + j) << 2);
+                tA[(4 * rq + j) * 16 + col] = (float)fma(0.5, (double)cx[j], 0.25 * (us + vv));
+            }
+            wave_sync();
+            double tq = 0.0;
+#pragma unroll 1
+            for (int blk = 0; blk < 4; ++blk) {
+                f4v t[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    t[u] = *reinterpret_cast<const f4v*>(tA + (4 * blk + u) * 16 + rq * 4);
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        t[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            tU[(4 * s + rq) * 16 + 4 * blk + u] + vr32[s], qr32[s], t[u], 0, 0, 0);
+                float mm = fminf(fminf(t[0][0], t[0][1]), fminf(t[0][2], t[0][3]));
+#pragma unroll
+                for (int u = 1; u < 4; ++u)
+                    mm = fminf(mm, fminf(fminf(t[u][0], t[u][1]), fminf(t[u][2], t[u][3])));
+                mm = fminf(mm, __int_as_float(__builtin_amdgcn_ds_bpermute(xaddr16, __float_as_int(mm))));
+                mm = fminf(mm, __int_as_float(__builtin_amdgcn_ds_bpermute(xaddr32, __float_as_int(mm))));
+                if (rq == blk) tq = ((double)mm + qq) - margin;
+            }
+            tri_lane = fmax(tri_lane, tq);
+        }
+    };
+
     const double hard_bound = d0 + 1e-10 * cscale_d + 1e-300;
     unsigned groups = 0;             // wave-uniform count of issued tile groups
+    unsigned reached = 0;            // ... and of tile groups that reached the screen
     // column tiles whose exact bound (column_tile_bounds) admits the skip bound as it stands
     // now; the bound only falls during the sweep, so each is checked again when reached
     unsigned long long ktmask = ~0ull;
@@ -958,6 +1102,22 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
         if (lbp[kt] > ((MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d) + lb_margin)
             continue;
         unsigned rowmask = 0xffffu;
+        if constexpr (V16) {
+            // per-group bounds: built once kTriGate groups of the symbol have reached the screen
+            // (the later E-steps' symbols, with a group or two left, never pay for the tables);
+            // a column tile whose four groups are all dead is left before its setup
+            if (c.tri && !tri_have && (c.tri == 2 || reached >= kTriGate)) {
+                build_tri();
+                tri_have = true;
+            }
+            if (tri_have) {
+                const double lim = (MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d;
+                const unsigned long long lv = __ballot(tri_lane <= lim) >> kt;   // bit 16 blk: group alive
+                if (!(lv & 0x0001000100010001ull)) continue;
+                rowmask = ((lv & 1) ? 0x000fu : 0u) | ((lv >> 16 & 1) ? 0x00f0u : 0u) |
+                          ((lv >> 32 & 1) ? 0x0f00u : 0u) | ((lv >> 48 & 1) ? 0xf000u : 0u);
+            }
+        }
         if (rowb) {
             double bnd = INFINITY;
             if (lane < 16) {
@@ -966,7 +1126,7 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                 bnd = fma(cabs2(x0), s_tab[63], rk[0] - 2.0 * (x0.x * rk[1] + x0.y * rk[2]));
             }
             const double lim = ((MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d) + lb_margin;
-            rowmask = (unsigned)__ballot(bnd <= lim);
+            rowmask &= (unsigned)__ballot(bnd <= lim);
             if (!rowmask) continue;                      // no row tile of this column survives
         }
         const int k = kt * 16 + col;
@@ -1081,6 +1241,14 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                 // TU independent 16x16 tiles in flight: STEPS*TU MFMAs per group;
                 // accumulators start at alpha_i, gamma_k (lane constant) stays outside
                 if (V16 && !((rowmask >> tg) & ((1u << TU) - 1u))) continue;
+                if constexpr (V16) {
+                    // again as the group is reached (the skip bound falls inside a column tile
+                    // too; hard: the lanes' own running minima)
+                    if (tri_have && !__any(lane_d(tri_lane, kt + 4 * tg) <=
+                                           ((MODE == SBCE_ESTEP_HARD) ? best_d : mshift + thr_d)))
+                        continue;
+                }
+                ++reached;
                 if (V16 && scr_on) {
                     f4v s32[TU];
 #pragma unroll
@@ -1267,7 +1435,10 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
         for (int q = 0; q < NA; ++q) tot_X[q][1] = cmulc(tot_muA[q], x3);
     }
 
-    if (c.count && lane == 0) atomicAdd(&g_estep_mfma, (unsigned long long)groups * STEPS * TU);
+    if (c.count && lane == 0) {
+        atomicAdd(&g_estep_mfma, (unsigned long long)groups * STEPS * TU);
+        if (V16) atomicAdd(&g_estep_groups, (unsigned long long)reached);
+    }
     constexpr int MS = NT + NT * NT;
     cd* out = a.mom + (size_t)gsym * MS;
     // The moment-repeat fold (armed by a.mchg): the lane that stores output word `lane` loads the
@@ -2354,6 +2525,7 @@ bool make_mfma(const Problem& pb, MfmaConst& c, size_t& lds, long& blocks) {
     c.tab_d = mfma_tab_d(NO, c.chunk, steps, pb.M, c.nkt_pad, c.rec_words);
     c.spw = 4;                                           // symbols per wave
     c.screen = !g_debug.estep_nof32;                     // FP32 tile-group screen (V16)
+    c.tri = g_debug.estep_tri;                           // per-group bounds (V16)
     c.rowb = pb.NT == 4 && c.prune;
     lds = 64 * sizeof(cd) + (size_t)kMfmaWaves * c.tab_d * sizeof(double);
     const long nsym = (long)pb.B * pb.Td;
@@ -2503,6 +2675,15 @@ hipError_t estep_debug_mfma(unsigned long long* out, int reset) {
         return hipMemcpyToSymbol(HIP_SYMBOL(g_estep_mfma), &z, sizeof(z), 0, hipMemcpyHostToDevice);
     }
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_estep_mfma), sizeof(*out), 0,
+                               hipMemcpyDeviceToHost);
+}
+
+hipError_t estep_debug_groups(unsigned long long* out, int reset) {
+    if (reset) {
+        const unsigned long long z = 0;
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_estep_groups), &z, sizeof(z), 0, hipMemcpyHostToDevice);
+    }
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_estep_groups), sizeof(*out), 0,
                                hipMemcpyDeviceToHost);
 }
 

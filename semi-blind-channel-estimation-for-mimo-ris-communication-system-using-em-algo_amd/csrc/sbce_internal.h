@@ -267,9 +267,12 @@ struct DebugConfig {
                          //                        one wave per symbol too; =t / =q the PM one thread /
                          //                        one quad per symbol at any size (all bitwise the
                          //                        same results; not flagged)
+    int estep_tri;       // SBCE_ESTEP_TRI=0|1|2   V16 sweep: per-group bounds T_3 / T_1 off / built once
+                         //                        a symbol's groups keep reaching the screen (the
+                         //                        default) / built for every swept symbol
 };
 inline constexpr DebugConfig kDebugDefault = {false, false, false, false, false, 128, false, false,
-                                              false, true, false, false, false, 0, false, 0};
+                                              false, true, false, false, false, 0, false, 0, 1};
 #if SBCE_AB
 extern DebugConfig g_debug;
 #else
@@ -555,6 +558,7 @@ hipError_t launch_sup_shift_mom(const Problem& pb, cd* mom, const cd* xsup, cons
 hipError_t launch_ser(const Problem& pb, const cd* xdest, const cd* xtrue, double* out,
                       hipStream_t s);
 hipError_t estep_debug_mfma(unsigned long long* out, int reset);   // SBCE_ESTEP_COUNT=1
+hipError_t estep_debug_groups(unsigned long long* out, int reset); // SBCE_ESTEP_COUNT=1
 // every kernel launch_estep launches for (pb, mode) that writes moments folds EstepArgs::mchg
 bool estep_momfold_supported(const Problem& pb, int mode);
 // A/B build: trial-M-steps the moment-repeat rule skipped since the last reset (chol.hip)
