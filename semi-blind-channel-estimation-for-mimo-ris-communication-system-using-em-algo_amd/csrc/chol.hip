@@ -3,25 +3,27 @@
 // LAPACK zgesv on the K x K system) by a Cholesky factorisation of the L x L
 // Hermitian R (commutation_matrix.py:3-8 identity, SURVEY.md §8 preamble).
 //
-// Both kernels are left-looking blocked Cholesky with panel width NB = 16 and a
-// fused forward substitution y = L^{-1} B^H, followed by a blocked back
-// substitution L^H x = y; they differ in how the panel update
-//     A[i, jb:jb+16] -= L[i, 0:jb] L[jb:jb+16, 0:jb]^H        (i >= jb)
-// and the panel TRSM run:
+// Every kernel here is a piece of a left-looking blocked Cholesky over 16-column sub-panels,
+//     A[i, jb:jb+16] -= L[i, 0:jb] L[jb:jb+16, 0:jb]^H        (i >= jb),
+// a TRSM of the panel rows against the factored 16 x 16 diagonal block, the forward
+// substitution y = L^{-1} B^H and the blocked back substitution L^H x = y.  Who runs what
+// (launch_chol_solve):
 //
-//   chol_mfma_kernel (L <= 512, default): the trailing rows are cut into 16-row
-//     tiles owned round-robin by the waves; each tile's 16 x 16 complex update is
-//     4 chained v_mfma_f64_16x16x4f64 per 4 columns of k (re/im split), with the
-//     panel's top block L[jb:jb+16, k-chunk] staged once in LDS as the shared B
-//     operand and the tile rows streamed from R as the A operand.  The TRSM
-//     X = A D^{-H} is 16 more MFMAs per tile.  The MFMA operands cost 2 loads per
-//     64 FMAs instead of 17 per 16 for the per-row VALU form.
-//   chol_solve_kernel (VALU, L <= 1024): thread per panel row, row register-resident.
+//   L <= 512 (default): the batched panel kernels, one launch per 32-column panel step over
+//     all trials -- panel_update2_kernel, panel_factor_kernel, then backsub4_kernel
+//     (L <= 272, n_rx <= 4) or backsub_kernel ("batched panel kernels" below).  A 16 x 16
+//     complex tile update is 4 chained v_mfma_f64_16x16x4f64 per 4 columns of k (re/im split,
+//     3 with the Gauss products), the panel's top rows staged in LDS as the shared B operand
+//     and the tile rows streamed from R as the A operand; the TRSM is 16 more MFMAs per tile.
+//   L > 512 and the min-norm solve: the 64 x 64 tiled path of mstep_large.hip / minnorm.hip,
+//     which calls launch_chol_tile -> chol_mfma_kernel to factor one diagonal tile in place.
+//   chol_solve_kernel (VALU, L <= 1024, SBCE_CHOL_IMPL=valu): one workgroup per trial, thread
+//     per panel row, row register-resident; the cross-check the tests compare the others with.
 //
-// The 16 x 16 diagonal block is factored by ONE wave in registers (lane r holds
-// row r) with wave-level syncs only; its inverse D^{-1} (lower) drives the TRSM
-// and both triangular block solves (conj(D^{-1}) is kept in R's unused strict
-// upper diagonal block for the back substitution).
+// The 16 x 16 diagonal block is factored by ONE wave with wave-level syncs only (in registers,
+// factor_diag, in the VALU kernel; in LDS, factor_diag_lds, in the MFMA kernels); its inverse
+// D^{-1} (lower) drives the TRSM and both triangular block solves (conj(D^{-1}) is kept in R's
+// unused strict upper diagonal block for the back substitution).
 // Pivots <= 1e-14 * max(diag R) are flagged (status bit 0) and their direction is dropped
 // (column zeroed, y and x components 0) in every public solve mode.  A clamp (pivot raised to
 // sqrt(tol), the column kept) is unstable on a rank-deficient R: past the numerical rank the
@@ -310,8 +312,10 @@ __global__ __launch_bounds__(512) void chol_solve_kernel(MstepArgs a, int L, int
                        ((skip & 31) ? SBCE_STATUS_DEBUG : 0);
 }
 
-// ---------------------------------------------------------------- MFMA kernel
-// Tile tau (rows jb + 16 tau ..) of panel jb belongs to wave tau % nw, slot tau / nw.
+// ---------------------------------------------------------------- MFMA pieces, tile factor
+// Shared by the batched panel kernels and chol_mfma_kernel (factor_diag_lds, diag_inverse_rd),
+// then backsub_kernel's substitution and chol_mfma_kernel itself: the in-place factor of one
+// diagonal tile (<= 64 x 64) of the tiled path, launched by launch_chol_tile.
 // Lane l of a 16 x 16 f64 MFMA: A[i = l&15][k = l>>4], B[k = l>>4][j = l&15],
 // C/D value q at row (l>>4) + 4q, column l&15.
 constexpr int KCM = 16;                // k-chunk of the A-operand register pipeline
@@ -382,10 +386,8 @@ __device__ __forceinline__ void diag_inverse_rd(const cd* A, cd* Di, const doubl
 // multiplied into a lower entry: it may hold the workspace's old contents (NaN included).
 __device__ __forceinline__ void factor_diag_lds(cd* A, int w, int lane, double tol,
                                                 int solve_mode, cd* Di, double* dinv, int* flag,
-                                                cd* Rdiag, int L,
-                                                unsigned long long* clk = nullptr) {
+                                                cd* Rdiag, int L) {
     const int col = lane & 15, r0 = lane >> 4;
-    unsigned long long tc = clk ? __builtin_amdgcn_s_memtime() : 0;
     bool bad_any = false, near_any = false;
 #pragma unroll 1
     for (int c = 0; c < w; ++c) {
@@ -409,7 +411,6 @@ __device__ __forceinline__ void factor_diag_lds(cd* A, int w, int lane, double t
         const double piv = drop ? 0.0 : pv * rs;
         const double inv = drop ? 0.0 : rs;
         const cd lcs = cscale(cconj(lc), inv * inv);
-        if (clk && lane == 0) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); clk[9] += t2 - tc; tc = t2; }
         wave_sync();                                         // all reads of column c done
         dinv[c] = inv;                                       // same value from every lane
         const bool gt = col > c, eq = col == c;
@@ -427,13 +428,10 @@ __device__ __forceinline__ void factor_diag_lds(cd* A, int w, int lane, double t
             if (eq && r0 == (c & 3)) A[c * NB + c] = cmk(piv, 0.0);
         }
         wave_sync();
-        if (clk && lane == 0) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); clk[10] += t2 - tc; tc = t2; }
     }
     if (bad_any) *flag |= 1;
     if (near_any) *flag |= 2;
-    if (clk && lane == 0) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); clk[0] += t2 - tc; tc = t2; }
     diag_inverse_rd(A, Di, dinv, w, lane);
-    if (clk && lane == 0) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); clk[1] += t2 - tc; tc = t2; }
     // factor rows (c <= r) and conj(Di[c][r]) (c > r) into R's diagonal block
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
@@ -441,49 +439,40 @@ __device__ __forceinline__ void factor_diag_lds(cd* A, int w, int lane, double t
         if (r < w && col < w)
             Rdiag[(size_t)r * L + col] = csel(col <= r, A[r * NB + col], cconj(Di[col * NB + r]));
     }
-    if (clk && lane == 0) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); clk[8] += t2 - tc; }
 }
 
-// Blocked back substitution L^H x = y for the MFMA kernel: every thread owns column
-// k = tid (+ nth) of the update and loads its 16 factor entries BEFORE the barrier that
-// publishes the block solution, so each block pays one memory latency, not three.
-template <int H = 2>     // rows k of the update per thread (H * nth >= L)
+// Blocked back substitution L^H x = y of backsub_kernel (nth = 256 threads, L <= 2 nth): every
+// thread owns columns k = tid and tid + nth of the update and loads its 16 factor entries of
+// each BEFORE the barrier that publishes the block solution, so each block pays one memory
+// latency, not three.
 __device__ __forceinline__ void back_substitute_pf(const cd* R, cd* y, int L, int NR, int tid,
                                                    int nth, int lane, int wave, int kb_stop,
                                                    int ld, cd* dblk) {
     // dblk: LDS [NB][NB] scratch for the diagonal block (its rows hold L[c][c] on the
     // diagonal and conj(Di[c2][c]) above it), loaded by the whole workgroup at once
     const int nblk = (L + NB - 1) / NB;
-    // diagonal blocks are prefetched one step ahead (one entry per thread when nth >= 256)
-    const bool pf = nth >= NB * NB;
+    // diagonal blocks are prefetched one step ahead, one entry per thread (nth = NB * NB)
     auto dload = [&](int kb) {
         const int k0 = kb * NB, w = (L - k0) < NB ? (L - k0) : NB;
         const int c = (tid >> 4) & 15, c2 = tid & 15;
-        return (kb >= 0 && tid < NB * NB && c < w && c2 < w && c2 >= c)
+        return (kb >= 0 && c < w && c2 < w && c2 >= c)
                    ? R[(size_t)(k0 + c) * ld + k0 + c2] : czero();
     };
-    cd dnext = pf ? dload(nblk - 1) : czero();
+    cd dnext = dload(nblk - 1);
     for (int kb = nblk - 1; kb >= kb_stop; --kb) {
         const int k0 = kb * NB;
         const int w = (L - k0) < NB ? (L - k0) : NB;
         // prefetch: conj(L[k0+c][k]) for this thread's columns k < k0
-        cd lv[H][NB];
+        cd lv[2][NB];
 #pragma unroll
-        for (int h = 0; h < H; ++h) {
+        for (int h = 0; h < 2; ++h) {
             const int k = tid + h * nth;
 #pragma unroll
             for (int c = 0; c < NB; ++c)
                 lv[h][c] = (k < k0 && c < w) ? R[(size_t)(k0 + c) * ld + k] : czero();
         }
-        if (pf) {
-            if (tid < NB * NB) dblk[tid] = dnext;
-            dnext = dload(kb - 1);
-        } else {
-            for (int e = tid; e < NB * NB; e += nth) {
-                const int c = e >> 4, c2 = e & 15;
-                dblk[e] = (c < w && c2 < w && c2 >= c) ? R[(size_t)(k0 + c) * ld + k0 + c2] : czero();
-            }
-        }
+        dblk[tid] = dnext;
+        dnext = dload(kb - 1);
         __syncthreads();
         if (wave == 0) {
             // x_blk = D^{-H} z_blk:  x[c] = z[c] / L[c][c] + sum_{c2>c} conj(Di[c2][c]) z[c2]
@@ -507,7 +496,7 @@ __device__ __forceinline__ void back_substitute_pf(const cd* R, cd* y, int L, in
         }
         __syncthreads();
 #pragma unroll
-        for (int h = 0; h < H; ++h) {
+        for (int h = 0; h < 2; ++h) {
             const int k = tid + h * nth;
             if (k < k0) {
                 for (int r = 0; r < NR; ++r) {
@@ -523,7 +512,9 @@ __device__ __forceinline__ void back_substitute_pf(const cd* R, cd* y, int L, in
     }
 }
 
-// DIAGNOSTIC (skip & 64): per-phase s_memtime sums of waves 0 and 1 of block 0
+// DIAGNOSTIC (skip & 64): per-phase s_memtime sums of waves 0 and 1 of trial 0, written by
+// panel_factor_body into words 16-31.  Words 0-15 are never written; the 32-word layout is what
+// sbce_debug_chol_clock's callers read.
 __device__ unsigned long long g_chol_clk[32];
 
 // DIAGNOSTIC phase-skip mask of the Cholesky kernels (timing only, results invalid).  Set
@@ -536,27 +527,27 @@ int g_chol_skip = 0;
 constexpr int g_chol_skip = 0;
 #endif
 
-// Geometry of one chol_mfma_kernel launch: the factored L x L matrix starts at row/col
-// `off` of trial b's matrix (a.R + b*stride), leading dimension ld.  SOLVE = false
-// factors in place only (a diagonal tile of the large-L path, tol from tolp[b]).
+// Geometry of one chol_mfma_kernel launch: the factored L x L tile starts at row/col `off` of
+// trial b's matrix (a.R + b*stride), leading dimension ld; tol from tolp[b].
 struct CholGeom {
     int ld, off;
     size_t stride;
     const double* tolp;
-    const int32_t* ext;    // SOLVE = false: per-trial active columns (null: all); tiles at or
-                           // past ext[b] are left untouched (min-norm path, minnorm.hip)
+    const int32_t* ext;    // per-trial active columns (null: all); tiles at or past ext[b] are
+                           // left untouched (min-norm path, minnorm.hip)
 };
 
-template <int MAXT, bool YLDS, int NWB, int KB, bool SOLVE = true>
-__global__ __launch_bounds__(64 * NWB) __attribute__((amdgpu_waves_per_eu(2)))
-void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
-    constexpr int KBP = KB + 1;                 // padded LDS row (complex) of the panel block
+constexpr int KBT = 128;               // k-block of the staged panel rows
+
+// In-place factorisation of one L x L diagonal tile (L <= 64) per workgroup: one wave per
+// 16-row tile (blockDim = 64 * ceil(L / 16)), wave tau owns row tile tau of every panel.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+void chol_mfma_kernel(MstepArgs a, int L, CholGeom g) {
+    constexpr int KBP = KBT + 1;                // padded LDS row (complex) of the panel block
     const int ld = g.ld;
-    // skip: DIAGNOSTIC phase mask (timing only, results invalid): 1 update, 2 diag factor,
-    // 8 trsm tiles, 16 back substitution
     const int b = blockIdx.x;
     if (a.done && a.done[b]) return;
-    if (!SOLVE && g.ext && g.off >= g.ext[b]) return;
+    if (g.ext && g.off >= g.ext[b]) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, nth = blockDim.x;
     const int lane = tid & 63, nw = nth >> 6;
@@ -564,67 +555,41 @@ void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
     cd* Bp = reinterpret_cast<cd*>(smem);       // [NB][KBP]  panel top rows, one k-block
     cd* Di = Bp + NB * KBP;                     // [NB][NB]
     cd* Xs = Di + NB * NB;                      // [nw][NB][NB] per-wave tile scratch
-    double* red = reinterpret_cast<double*>(Xs + nw * NB * NB);   // [16]
-    int* flag = reinterpret_cast<int*>(red + 16);
-    cd* ylds = reinterpret_cast<cd*>(red + 18);
+    double* dinv = reinterpret_cast<double*>(Xs + nw * NB * NB);   // [16]
+    int* flag = reinterpret_cast<int*>(dinv + 16);
     cd* R = a.R + (size_t)b * g.stride + (size_t)g.off * ld + g.off;
-    cd* y = SOLVE ? (YLDS ? ylds : a.rhs + (size_t)b * L * NR) : nullptr;
     cd* X = Xs + wave * NB * NB;
-    double tol;
-    if (SOLVE) {
-        tol = prologue<YLDS>(R, a.rhs + (size_t)b * L * NR, y, red, flag, L, NR, tid, nth, lane,
-                             wave);
-    } else {
-        tol = g.tolp[b];
-        if (tid == 0) *flag = 0;
-        __syncthreads();
-    }
+    const double tol = g.tolp[b];
+    if (tid == 0) *flag = 0;
+    __syncthreads();
     const int li = lane & 15, lk = lane >> 4;
-    const bool clk = (skip & 64) && b == 0 && wave < 2 && lane == 0;
-    unsigned long long tclk = clk ? __builtin_amdgcn_s_memtime() : 0;
-#define SBCE_CLK(ph)                                                          \
-    if (clk) {                                                                \
-        const unsigned long long t2 = __builtin_amdgcn_s_memtime();           \
-        g_chol_clk[wave * 8 + (ph)] += t2 - tclk;                             \
-        tclk = t2;                                                            \
-    }
 
     for (int jb = 0; jb < L; jb += NB) {
         const int w = (L - jb) < NB ? (L - jb) : NB;
         const int ntile = (L - jb + NB - 1) / NB;
-        const int nact = (ntile - wave + nw - 1) / nw;     // active tile slots of this wave
-        // A-operand rows of this wave's tiles (rows past L read row L-1: harmless)
-        const cd* arow[MAXT];
+        const bool act = wave < ntile;                     // this wave's tile is in the panel
+        // A-operand rows of this wave's tile (rows past L read row L-1: harmless)
+        int ar = jb + wave * NB + li;
+        ar = ar < L ? ar : L - 1;
+        const cd* arow = R + (size_t)ar * ld + lk;
+        // ---- C tile <- A[rows, jb:jb+16] (C layout) ----
+        mf4 cre, cim;
 #pragma unroll
-        for (int u = 0; u < MAXT; ++u) {
-            int r = jb + (wave + u * nw) * NB + li;
-            r = r < L ? r : L - 1;
-            arow[u] = R + (size_t)r * ld + lk;
+        for (int q = 0; q < 4; ++q) {
+            const int r = jb + wave * NB + lk + 4 * q;
+            cd v = czero();
+            if (act && r < L && li < w) v = R[(size_t)r * ld + jb + li];
+            cre[q] = v.x;
+            cim[q] = v.y;
         }
-        // ---- C tiles <- A[rows, jb:jb+16] (C layout) ----
-        mf4 cre[MAXT], cim[MAXT];
-#pragma unroll
-        for (int u = 0; u < MAXT; ++u) {
-            const int tau = wave + u * nw;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = jb + tau * NB + lk + 4 * q;
-                cd v = czero();
-                if (tau < ntile && r < L && li < w) v = R[(size_t)r * ld + jb + li];
-                cre[u][q] = v.x;
-                cim[u][q] = v.y;
-            }
-        }
-        // ---- left-looking update over k-blocks of KBMAX columns: the panel's top rows
-        //      are staged once per block; each wave streams its tiles' rows with the next
+        // ---- left-looking update over k-blocks of KBT columns: the panel's top rows are
+        //      staged once per block; each wave streams its tile's rows with the next
         //      16-column chunk's loads in flight while the current chunk's MFMAs run ----
-        for (int kb0 = 0; kb0 < ((skip & 1) ? 0 : jb); kb0 += KB) {
-            const int kbs = (jb - kb0) < KB ? (jb - kb0) : KB;         // multiple of 16
-            cd av[MAXT][4];
+        for (int kb0 = 0; kb0 < jb; kb0 += KBT) {
+            const int kbs = (jb - kb0) < KBT ? (jb - kb0) : KBT;       // multiple of 16
+            cd av[4];
 #pragma unroll
-            for (int u = 0; u < MAXT; ++u)
-#pragma unroll
-                for (int s2 = 0; s2 < 4; ++s2) av[u][s2] = arow[u][kb0 + 4 * s2];
+            for (int s2 = 0; s2 < 4; ++s2) av[s2] = arow[kb0 + 4 * s2];
             __syncthreads();
             for (int e = tid; e < NB * kbs; e += nth) {
                 const int c = e / kbs, k = e - c * kbs;
@@ -632,68 +597,40 @@ void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
             }
             __syncthreads();
             for (int k0 = 0; k0 < kbs; k0 += KCM) {
-                // register pipeline (next chunk's loads in flight) only where the registers
-                // allow it; MAXT >= 4 relies on the second resident workgroup instead
-                constexpr bool PIPE = MAXT <= 3;
-                cd an[PIPE ? MAXT : 1][4];
+                cd an[4];
                 const bool more = k0 + KCM < kbs;
-                if (PIPE) {
 #pragma unroll
-                    for (int u = 0; u < MAXT; ++u)
-#pragma unroll
-                        for (int s2 = 0; s2 < 4; ++s2)
-                            an[PIPE ? u : 0][s2] = more ? arow[u][kb0 + k0 + KCM + 4 * s2] : czero();
-                } else if (k0 > 0) {
-#pragma unroll
-                    for (int u = 0; u < MAXT; ++u)
-#pragma unroll
-                        for (int s2 = 0; s2 < 4; ++s2) av[u][s2] = arow[u][kb0 + k0 + 4 * s2];
-                }
+                for (int s2 = 0; s2 < 4; ++s2) an[s2] = more ? arow[kb0 + k0 + KCM + 4 * s2] : czero();
 #pragma unroll
                 for (int s2 = 0; s2 < 4; ++s2) {
                     const cd t = Bp[li * KBP + k0 + 4 * s2 + lk];
-#pragma unroll
-                    for (int u = 0; u < MAXT; ++u) {
-                        if (u >= nact) break;          // wave-uniform (SGPR) bound: no exec masking
+                    if (act) {                         // wave-uniform (SGPR): no exec masking
                         // re -= ar tr + ai ti ;  im -= ai tr - ar ti
-                        const cd v = av[u][s2];
-                        cre[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.x, t.x, cre[u], 0, 0, 0);
-                        cre[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.y, t.y, cre[u], 0, 0, 0);
-                        cim[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.y, t.x, cim[u], 0, 0, 0);
-                        cim[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, t.y, cim[u], 0, 0, 0);
+                        const cd v = av[s2];
+                        cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.x, t.x, cre, 0, 0, 0);
+                        cre = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.y, t.y, cre, 0, 0, 0);
+                        cim = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.y, t.x, cim, 0, 0, 0);
+                        cim = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, t.y, cim, 0, 0, 0);
                     }
                 }
-                if (PIPE) {
 #pragma unroll
-                    for (int u = 0; u < MAXT; ++u)
-#pragma unroll
-                        for (int s2 = 0; s2 < 4; ++s2) av[u][s2] = an[PIPE ? u : 0][s2];
-                }
+                for (int s2 = 0; s2 < 4; ++s2) av[s2] = an[s2];
             }
         }
-        SBCE_CLK(0)
-        // ---- diagonal tile (tau = 0: wave 0, slot 0), factored in LDS ----
+        // ---- diagonal tile (wave 0), factored in LDS ----
         if (wave == 0) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) X[(lk + 4 * q) * NB + li] = cmk(cre[0][q], cim[0][q]);
+            for (int q = 0; q < 4; ++q) X[(lk + 4 * q) * NB + li] = cmk(cre[q], cim[q]);
             wave_sync();
-            if (!(skip & 2))
-                factor_diag_lds(X, w, lane, tol, a.solve_mode, Di, red, flag,
-                                R + (size_t)jb * ld + jb, ld, clk ? g_chol_clk + 6 : nullptr);
-            if (SOLVE) forward_y_block(Di, y + jb * NR, w, NR, lane);
+            factor_diag_lds(X, w, lane, tol, a.solve_mode, Di, dinv, flag, R + (size_t)jb * ld + jb, ld);
         }
-        SBCE_CLK(1)
         __syncthreads();
-        SBCE_CLK(2)
         // ---- TRSM X = C D^{-H} for the other tiles, as X^T = conj(Di) C^T (C transposed
         //      through the wave's LDS scratch); lane (li, lk) ends with X[li][lk + 4q] ----
+        if (wave != 0 && act) {
+            const int row0 = jb + wave * NB;
 #pragma unroll
-        for (int u = 0; u < MAXT; ++u) {
-            const int tau = wave + u * nw;
-            if (tau == 0 || tau >= ntile || (skip & 8)) continue;
-            const int row0 = jb + tau * NB;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) X[(lk + 4 * q) * NB + li] = cmk(cre[u][q], cim[u][q]);
+            for (int q = 0; q < 4; ++q) X[(lk + 4 * q) * NB + li] = cmk(cre[q], cim[q]);
             wave_sync();
             mf4 xre = {0.0, 0.0, 0.0, 0.0}, xim = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -708,53 +645,32 @@ void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
             }
             const bool live = row0 + li < L;
             cd* crow = R + (size_t)(live ? row0 + li : L - 1) * ld + jb;
-            cd xv[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int j = lk + 4 * q;
-                xv[q] = cmk(xre[q], xim[q]);
-                if (live && j < w) crow[j] = xv[q];
+                if (live && j < w) crow[j] = cmk(xre[q], xim[q]);
             }
-            // y[row0+li] -= sum_j X[li][j] y_blk[j]: 4 columns per lane, reduced over lk
-            for (int r = 0; r < (SOLVE ? NR : 0); ++r) {
-                cd p = czero();
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int j = lk + 4 * q;
-                    if (j < w) p = cfma(p, xv[q], y[(jb + j) * NR + r]);
-                }
-                p.x += shfl_xor_d(p.x, 16); p.y += shfl_xor_d(p.y, 16);
-                p.x += shfl_xor_d(p.x, 32); p.y += shfl_xor_d(p.y, 32);
-                if (lk == 0 && live) y[(row0 + li) * NR + r] = csub(y[(row0 + li) * NR + r], p);
-            }
-            wave_sync();
         }
-        SBCE_CLK(3)
         __syncthreads();
-        SBCE_CLK(4)
     }
-    if (SOLVE) {
-        back_substitute_pf(R, y, L, NR, tid, nth, lane, wave, (skip & 16) ? (L + NB - 1) / NB : 0,
-                           ld, Di);
-        SBCE_CLK(5)
-        cd* th = a.theta + (size_t)b * L * NR;
-        for (int e = tid; e < L * NR; e += nth) th[e] = cconj(y[e]);
-    }
-#undef SBCE_CLK
+    // the pivot flags: bit 0 a dropped / clamped pivot, bit 1 the min-norm path's rank flag
     if (tid == 0 && a.status)
-        a.status[b] |= ((*flag & 1) ? a.clamp_status : 0) | ((*flag & 2) ? SBCE_STATUS_RANK : 0) |
-                       ((skip & 31) ? SBCE_STATUS_DEBUG : 0);
+        a.status[b] |= ((*flag & 1) ? a.clamp_status : 0) | ((*flag & 2) ? SBCE_STATUS_RANK : 0);
 }
 
+
 // ---------------------------------------------------------------- batched panel kernels
-// The same left-looking blocked factorisation and fused forward substitution as
-// chol_mfma_kernel, but one LAUNCH per 32-column panel step over every trial instead of
-// one workgroup walking all panels of its trial: the panel update is a batched GEMM with
-// one wave per 16-row tile (high occupancy hides the streamed rows' latency), the serial
-// diagonal factors of ~1000 trials run side by side in the factor launch, and no kernel
-// needs the register budget of a whole trial's tiles.  y lives in the rhs buffer.
+// The solve for L <= 512 (launch_chol_batched): a left-looking blocked factorisation with the
+// forward substitution fused, one LAUNCH per 32-column panel step over every trial (not one
+// workgroup walking all panels of its trial): the panel update is a batched GEMM with one wave
+// per 16-row tile (high occupancy hides the streamed rows' latency), the serial diagonal
+// factors of ~1000 trials run side by side in the factor launch, and no kernel needs the
+// register budget of a whole trial's tiles.  y lives in the rhs buffer.  Per panel j:
+//   panel_update2_kernel (even j >= 2)  updates panels j and j+1 by the columns [0, jb);
+//   panel_factor_kernel                 factors panel j (odd j: after its rank-32 pre-update);
+// then backsub4_kernel (L <= 272, n_rx <= 4) or backsub_kernel.
 //
-// panel_update_kernel (jb > 0): C_tau = A[rows tau, jb:jb+32] - L[rows tau, 0:jb] L[jb:jb+32, 0:jb]^H
+// panel_update_body: C_tau = A[rows tau, jb:jb+32] - L[rows tau, 0:kend] L[jb:jb+32, 0:kend]^H
 // for the 16-row tiles tau = 0.. of panel jb; block = NWU waves = NWU row tiles of ONE trial,
 // the panel's top rows staged per KBU-column chunk in LDS by LDS-DMA (shared B operand),
 // each wave's rows streamed from R with the next 16 columns in flight; every A value
@@ -762,10 +678,11 @@ void chol_mfma_kernel(MstepArgs a, int L, int NR, int skip, CholGeom g) {
 // Blocks of one trial sit on one XCD.
 constexpr int KBU = 64;
 constexpr int PW = 32;    // panel width: two 16-column sub-panels
+constexpr int NWU = 4;    // waves (= row tiles) of an update block
 // Body of the update of trial b, row-tile group grp, by the columns [0, kend) (kend = jb: the
 // whole left part; the look-ahead step passes kend = jb - PW).  Bp: PW * (KBU + 1) LDS entries.
 // G3: the complex products by three real MFMAs instead of four (csub_step, sbce_internal.h).
-template <int NWU, bool G3 = false>
+template <bool G3 = false>
 __device__ __forceinline__ void panel_update_body(const MstepArgs& a, int L, int jb, int kend, int ntile,
                                                   int b, int grp, int skip, cd* Bp, int kbeg = 0) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -872,8 +789,8 @@ __global__ __launch_bounds__(256) void panel_update2_kernel(MstepArgs a, int L, 
     const int b = (slot / gpt) * 8 + xcd, g = slot - (slot / gpt) * gpt;
     if (b >= a.nbatch) return;
     if (mstep_skip(a, b)) return;
-    if (g < gpt0) panel_update_body<4, G3>(a, L, jb, jb, ntile, b, g, skip, Bp);
-    else panel_update_body<4, G3>(a, L, jb + PW, jb, ntile - 2, b, g - gpt0, skip, Bp);
+    if (g < gpt0) panel_update_body<G3>(a, L, jb, jb, ntile, b, g, skip, Bp);
+    else panel_update_body<G3>(a, L, jb + PW, jb, ntile - 2, b, g - gpt0, skip, Bp);
 }
 
 // 16 x 16 tile of R (rows row0.., columns c0.., w valid columns) into per-lane registers:
@@ -1452,7 +1369,7 @@ __global__ __launch_bounds__(256) void backsub_kernel(MstepArgs a, int L, int NR
     __syncthreads();
     // every thread has read the trial's word: cleared for the next E-step
     if (a.mchg && tid == 0) a.mchg[b] = 0;
-    back_substitute_pf<2>(R, y, L, NR, tid, nth, lane, wave, (skip & 16) ? (L + NB - 1) / NB : 0, L,
+    back_substitute_pf(R, y, L, NR, tid, nth, lane, wave, (skip & 16) ? (L + NB - 1) / NB : 0, L,
                           y + L * NR);
     cd* th = a.theta + (size_t)b * L * NR;
     if (a.freeze_w) {                                        // the fixed-point fold (backsub4_kernel)
@@ -1913,10 +1830,10 @@ hipError_t launch_chol_tile(const Problem& pb, const MstepArgs& a, int k0, int w
     const int ntile = (w + NB - 1) / NB;             // <= 4 -> one 16-row tile per wave
     CholGeom geo;
     geo.ld = pb.L; geo.off = k0; geo.stride = (size_t)pb.L * pb.L; geo.tolp = a.tol; geo.ext = ext;
-    const size_t lds = (size_t)(NB * (128 + 1) + NB * NB + ntile * NB * NB) * sizeof(cd) +
+    // Bp, Di, one scratch tile per wave, dinv[16], the status flag
+    const size_t lds = (size_t)(NB * (KBT + 1) + NB * NB + ntile * NB * NB) * sizeof(cd) +
                        18 * sizeof(double);
-    hipLaunchKernelGGL((chol_mfma_kernel<1, false, 4, 128, false>), dim3(pb.B), dim3(64 * ntile),
-                       lds, s, a, w, pb.NR, 0, geo);
+    hipLaunchKernelGGL(chol_mfma_kernel, dim3(pb.B), dim3(64 * ntile), lds, s, a, w, geo);
     return hipGetLastError();
 }
 

@@ -35,7 +35,6 @@ namespace sbce {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
 constexpr int kCH = 4;              // i-values per inner chunk
 constexpr double kSkipThr = 50.0;   // skip weights below e^-50 of the running max
@@ -649,6 +648,7 @@ __device__ unsigned long long g_estep_groups;
 
 template <int NT, int NR, int MODE, int TU, bool V16>
 __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaConst& c) {
+    static_assert(!V16 || NT == 4, "the V16 body is the n_tx = 4, M = 16 sweep");
     // V16 (n_tx = 4, M = 16): the layout constants are compile-time (LDS offsets fold into
     // immediates, one SGPR wave base); otherwise they come from MfmaConst
     const int k_M = V16 ? 16 : c.M;
@@ -2538,18 +2538,20 @@ template <int NT, int NR>
 hipError_t dispatch_mfma_mode(const MfmaConst& c, size_t lds, long blocks, const EstepArgs& a,
                               int mode, hipStream_t s) {
     const bool tu4 = (c.chunk / 16) % 4 == 0;
-    if (NT == 4 && c.M == 16 && tu4) {            // cfg1 geometry: hoisted V operand
-        // the V16 body takes these layout constants as compile-time values
-        if (c.JA != 256 || c.JB != 256 || c.chunk != 256 || c.nkt_pad != 16 ||
-            c.prep_stride != 4 + 2 * NT * NR + 16 + 6 * NR)
-            return hipErrorInvalidValue;
-        if (mode == SBCE_ESTEP_HARD)
-            hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_HARD, 4, true>),
-                               dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
-        else
-            hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_SOFT, 4, true>),
-                               dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
-        return hipGetLastError();
+    if constexpr (NT == 4) {                      // the V16 body exists for n_tx = 4 alone
+        if (c.M == 16 && tu4) {                   // cfg1 geometry: hoisted V operand
+            // the V16 body takes these layout constants as compile-time values
+            if (c.JA != 256 || c.JB != 256 || c.chunk != 256 || c.nkt_pad != 16 ||
+                c.prep_stride != 4 + 2 * NT * NR + 16 + 6 * NR)
+                return hipErrorInvalidValue;
+            if (mode == SBCE_ESTEP_HARD)
+                hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_HARD, 4, true>),
+                                   dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
+            else
+                hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_SOFT, 4, true>),
+                                   dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
+            return hipGetLastError();
+        }
     }
     if (mode == SBCE_ESTEP_HARD) {
         if (tu4)

@@ -43,14 +43,7 @@ constexpr int kLanczosSteps = 4;   // lambda_max to ~10 % (the cut carries a 32x
 constexpr double kCutSafety = 32.0;   // tau = kCutSafety * cut (see the header comment)
 constexpr double kEps = 2.220446049250313e-16;   // numpy.finfo(float).eps
 
-// deterministic block reductions (256 threads, fixed tree order)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// deterministic block reduction (256 threads, fixed tree order)
 __device__ __forceinline__ double block_max(double v, double* red) {
     for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
     __syncthreads();

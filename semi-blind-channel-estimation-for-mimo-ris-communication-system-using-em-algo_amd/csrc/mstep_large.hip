@@ -15,7 +15,7 @@
 //                        the lower block triangle only (the factorisation never reads the
 //                        strict upper triangle);
 //   blocked right-looking Cholesky, NB = 64, per column block k:
-//     chol_mfma_kernel<SOLVE=false>  factors the 64 x 64 diagonal tile in place (chol.hip);
+//     chol_mfma_kernel               factors the 64 x 64 diagonal tile in place (chol.hip);
 //     tile_inverse_kernel            W = L_kk^{-1} (64 x 64, workspace);
 //     tile_gemm_kernel<TRSM>         L_ik = A_ik W^H             (i > k);
 //     tile_gemm_kernel<HERK>         A_ij -= L_ik L_jk^H          (i >= j > k);

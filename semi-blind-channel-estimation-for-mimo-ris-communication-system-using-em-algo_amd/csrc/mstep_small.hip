@@ -492,7 +492,6 @@ mstep_small2_build_kernel(MstepArgs a, int P, int Tp, int Td, int L) {
     constexpr int MS = NT + NT * NT;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T = Tp + Td;
     const cd* up = a.up + (size_t)b * Tp * L;
     const cd* yp = a.yp + (size_t)b * Tp * NR;
     const cd* ps = a.psid + (size_t)b * Td * P;
@@ -508,8 +507,6 @@ mstep_small2_build_kernel(MstepArgs a, int P, int Tp, int Td, int L) {
     const int bi = role >= 1 ? 1 : 0, bj = role == 2 ? 1 : 0;
     const int ca = li / NR, cr = li - ca * NR;      // B^H: column (a, r) of the product
     const bool con = li < NT * NR;
-    const int VP = bh ? NT * Tp : Tp;                // virtual symbols: pilot slots, then data
-    const int V = VP + Td;
     mf4 p1 = {0.0, 0.0, 0.0, 0.0}, p2 = p1, p3 = p1;
     auto mfma3 = [&](cd x, cd y) {
         p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x.x, y.x, p1, 0, 0, 0);
