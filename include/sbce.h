@@ -83,6 +83,37 @@ extern "C" {
                                    that term is kept as R += c 1 1^T, for n_rx >= 2 it cancels
                                    in the pseudo-inverse, see sbce_gauss_expand).  P = N rows of
                                    psi (no direct path); dims.varx used; cons ignored */
+#define SBCE_ESTEP_MMSE_SOFT 7  /* soft MMSE E-step for n_tx = 1..8: see SBCE_ESTEP_ZF_SOFT */
+#define SBCE_ESTEP_ZF_SOFT 8    /* soft ZF E-step.  Both soft modes (an additive extension of
+                                   ABI 7): per-stream linear equalisation and a Gaussian soft
+                                   demapper, O(n_tx^3 + n_tx M) per symbol -- the arithmetic of
+                                   sbce_detect_linear (below) inside the EM chain.  Per (b, t) on the
+                                   CLEAN effective channel H_t[r][a] = sum_p psi_d[b][t][p]
+                                   theta[b][(p n_tx + a) n_rx + r] (not the reference's off-by-one
+                                   channel of SBCE_ESTEP_ZF / _MMSE), with s2 = varn_b^2 (varn_t[b]
+                                   or dims.varn: the posterior denominator of every E-step here),
+                                   es = (sum_s |cons[s]|^2) / M (formed on the device from the
+                                   table), rho = s2 / es (MMSE) or 0 (ZF) and A = H^H H + rho I by
+                                   Cholesky: g, z, mu, x_soft and nu as documented for
+                                   sbce_detect_linear; post[a][s] ~ e^{-|x_soft_a - cons[s]|^2 / nu_a},
+                                   m_a = sum_s post cons, S[a][a] = sum_s post |cons|^2 and
+                                   S[a][c] = m_a conj(m_c) for a != c (a product posterior, so
+                                   S - m m^H = diag(var) >= 0 in sbce_em_noise).
+                                   Degenerate cases: a pivot <= 1e-14 max_a A_aa gives the whole
+                                   symbol the uniform posterior's moments and sets
+                                   SBCE_STATUS_DETECTOR; an MMSE stream with mu_a <= 0 gets the
+                                   uniform posterior for itself alone.  Every output is finite for
+                                   any s2 > 0.
+                                   Limits (decided before any HIP call): n_tx 1..8, n_rx 1..8, m a
+                                   power of two in 2..64, and n_rx >= n_tx for ZF_SOFT, else
+                                   SBCE_EUNSUPPORTED (also for n_tx or n_rx past 8); x_dest or x_sup
+                                   set: SBCE_EINVAL (no hard decisions, no superimposed pilots);
+                                   partition_r and varx are ignored.  Accepted by sbce_estep,
+                                   sbce_em, sbce_em_multi (the fixed-point rule applies as for any
+                                   mode), sbce_em_noise and sbce_em_conv (the theta rule at every
+                                   n_tx; ll_hist keeps sbce_loglik's own n_tx <= 4 limit).
+                                   Deterministic: trial b of a B-trial call is bitwise the B = 1
+                                   call, varn_t[b] == dims.varn gives the scalar call's bits */
 
 /* M-step solve modes (SURVEY.md §7 hard part 3) */
 #define SBCE_SOLVE_CHOL 0       /* Hermitian Cholesky of the reduced L x L system
@@ -115,7 +146,11 @@ extern "C" {
                                    rebuilt by the general (VALU) path (informational) */
 #define SBCE_STATUS_DETECTOR 4  /* ZF/MMSE: the reference's flattened argmin indexed past
                                    all_possibleSymbols (IndexError at
-                                   all_detectorsvsTd.py:52); row flat mod M^n_tx used */
+                                   all_detectorsvsTd.py:52); row flat mod M^n_tx used.
+                                   ZF_SOFT / MMSE_SOFT: a symbol's A = H^H H + rho I had a pivot
+                                   <= 1e-14 max_a A_aa; that symbol carries the uniform
+                                   posterior's moments (NONHPD stays the M-step's finding about R
+                                   in the chain's status word) */
 #define SBCE_STATUS_DEBUG 8     /* a diagnostic phase-skip mask (sbce_debug_chol_skip, not
                                    part of this header's API) or a non-default kernel selected
                                    by an SBCE_* debug environment variable was active */
@@ -128,7 +163,7 @@ extern "C" {
 
 typedef struct sbce_dims {
     int32_t batch;      /* B: independent Monte-Carlo trials */
-    int32_t n_tx;       /* streams (1..4 exact/hard E-step, 1..8 PM/ZF/MMSE E-steps) */
+    int32_t n_tx;       /* streams (1..4 exact/hard E-step, 1..8 PM/ZF/MMSE and soft ZF/MMSE) */
     int32_t n_rx;       /* receive antennas (1..8) */
     int32_t n_psi;      /* P = rows of PsiTilde_td (N+1 with the direct path) */
     int32_t t_p;        /* pilot symbols */
@@ -414,7 +449,7 @@ int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
 /* sbce_em with the noise parameter estimated: varn_est[b] starts at p->varn_t[b] (or d->varn) and
  * is the E-step's per-trial parameter; per iteration E-step, M-step, noise update, then the oracle
  * early stop (p->h_true), so a trial's last M-step is followed by its update.  p->workspace as for
- * sbce_em.  estep_mode: SOFT, HARD, PM, PM_SOFT, ZF, MMSE; SBCE_ESTEP_GAUSS gives
+ * sbce_em.  estep_mode: SOFT, HARD, PM, PM_SOFT, ZF, MMSE, MMSE_SOFT, ZF_SOFT; SBCE_ESTEP_GAUSS gives
  * SBCE_EUNSUPPORTED (its S_t is not a second moment).  Decided before any HIP call, beside
  * sbce_em's own checks -- SBCE_EINVAL: p->x_sup or p->llf set, null or misaligned (8 bytes)
  * varn_est, varn_hist or scratch, varn_min <= 0, flags != 0; SBCE_EWORKSPACE: scratch_bytes too

@@ -22,6 +22,8 @@ SBCE_ESTEP_PM_SOFT = 3
 SBCE_ESTEP_ZF = 4
 SBCE_ESTEP_MMSE = 5
 SBCE_ESTEP_GAUSS = 6
+SBCE_ESTEP_MMSE_SOFT = 7
+SBCE_ESTEP_ZF_SOFT = 8
 SBCE_SOLVE_CHOL = 0
 SBCE_SOLVE_CHOL_DROP = 1
 SBCE_SOLVE_MINNORM = 2

@@ -209,6 +209,14 @@ MstepArgs mstep_args(const Problem& pb, const sbce_ptrs* p, const void* moments,
     return ma;
 }
 
+// SBCE_ESTEP_MMSE_SOFT / ZF_SOFT report n_tx or n_rx past 8 as SBCE_EUNSUPPORTED, like
+// sbce_detect_linear, whose arithmetic they are (include/sbce.h); make_problem alone would say
+// SBCE_EINVAL, which stays the answer for every other mode.
+bool linear_oversize(const sbce_dims* d, int estep_mode) {
+    return d && estep_linear_mode(estep_mode) && d->n_tx >= 1 && d->n_rx >= 1 &&
+           (d->n_tx > 8 || d->n_rx > 8);
+}
+
 // The E-step's arguments: moments out, and the MFMA sweep's regions of the workspace carved by
 // `c` (null: no workspace, the sweep kernel prepares each symbol itself).
 EstepArgs estep_args(const sbce_ptrs* p, void* moments, char* ws, const Carve* c) {
@@ -399,6 +407,7 @@ struct EmChain {
         p = p_; nz = nz_; cv = cv_;
         iters = iters_; estep_mode = estep_mode_; solve_mode = solve_mode_;
         s = (hipStream_t)hip_stream;
+        if (linear_oversize(d, estep_mode)) return SBCE_EUNSUPPORTED;
         if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
         if ((nz || cv) && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
         if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
@@ -838,6 +847,7 @@ int sbce_estep(const sbce_dims* d, const sbce_ptrs* p, int estep_mode, void* mom
                void* hip_stream) {
     clear_stale_error();
     Problem pb;
+    if (linear_oversize(d, estep_mode)) return SBCE_EUNSUPPORTED;
     if (!make_problem(d, pb)) return SBCE_EINVAL;
     int rc = check_ptrs(p, pb, false);
     if (rc) return rc;

@@ -6,7 +6,8 @@
 //   ZF    x_soft_a = z_a,      nu_a = sigma2 g_a
 // and each stream is demapped on its own: d_s = |x_soft_a - cons[s]|^2, weights e^{-d_s / nu_a}.
 //
-// Work split.  One workgroup of 4 waves takes 32 consecutive symbols of ONE trial.
+// Work split (staging, solve and estimate are linear_solve.h's, shared with the soft ZF / MMSE
+// E-step of estep_linear.hip).  One workgroup of 4 waves takes 32 consecutive symbols of ONE trial.
 //   staging  theta of the trial goes through LDS in tiles of 32 rows of P (32 x 64 x 16 B = 32 KB)
 //            beside the tile's 32 x 32 phases of psi_d (16 KB), both by coalesced 16-byte loads.
 //            Wave w forms H of its 8 symbols: lane = (entry e of the NE = NT NR, symbol subset g);
@@ -30,28 +31,11 @@
 // workgroup reads another's results: trial b of a B-trial call is bitwise the B = 1 call.
 // Launches: one small kernel that zeroes err and status (when either is set), then the detection
 // kernel: a linear chain of two kernel nodes on the caller's stream, no memset node.
-#include "sbce_internal.h"
+#include "linear_solve.h"
 
 namespace sbce {
 
 namespace {
-
-constexpr int kLinThreads = 256;
-constexpr int kLinSym = 32;         // symbols per workgroup: 4 waves x 8 lane groups
-constexpr int kLinPT = 32;          // rows of P per staged tile
-constexpr int kLinMaxNE = 64;       // NT * NR
-constexpr int kLinHS = 65;          // row stride of H_s (one 16-byte slot of padding)
-constexpr int kLinBuf = kLinPT * kLinMaxNE + kLinSym * kLinPT;   // theta tile + psi tile >= 32 * 65
-
-__device__ __forceinline__ cd bperm_c(cd v, int addr) {
-    return cmk(bperm_d(v.x, addr), bperm_d(v.y, addr));
-}
-// max over each group of 8 lanes (quad xor 1, xor 2, then the mirrored quad)
-__device__ __forceinline__ double group8_max(double v) {
-    v = fmax(v, dpp_d<0xB1>(v));
-    v = fmax(v, dpp_d<0x4E>(v));
-    return fmax(v, dpp_d<0x141>(v));
-}
 
 template <int NT>
 __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a) {
@@ -75,46 +59,7 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
     if (tid < 3) cnt_s[tid] = 0;
 
     // ---- staging: H_t of the workgroup's symbols
-    {
-        cd* th_s = buf_s;
-        cd* psi_s = buf_s + kLinPT * kLinMaxNE;
-        const cd* th = a.theta + (size_t)b * P * NE;
-        int lgE = 0;
-        while ((1 << lgE) < NE) ++lgE;
-        const int ng = (64 >> lgE) < 8 ? (64 >> lgE) : 8;   // symbol subsets per wave
-        const int nj = 8 / ng;                              // symbols per lane
-        const int e = lane & ((1 << lgE) - 1), g = lane >> lgE;
-        const bool on = e < NE && g < ng;
-        cd acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = czero();
-        for (int p0 = 0; p0 < P; p0 += kLinPT) {
-            const int np = P - p0 < kLinPT ? P - p0 : kLinPT;
-            __syncthreads();
-            for (int i = tid; i < np * NE; i += kLinThreads) th_s[i] = th[(size_t)p0 * NE + i];
-            for (int i = tid; i < kLinSym * kLinPT; i += kLinThreads) {
-                const int k = i >> 5, pp = i & 31;
-                psi_s[i] = (t0 + k < tend && pp < np) ? a.psid[(bt + t0 + k) * P + p0 + pp] : czero();
-            }
-            __syncthreads();
-            if (on) {
-                const cd* ps = psi_s + (w * 8 + g) * kLinPT;
-                for (int pp = 0; pp < np; ++pp) {
-                    const cd tv = th_s[pp * NE + e];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (j < nj) acc[j] = cfma(acc[j], ps[j * ng * kLinPT + pp], tv);
-                }
-            }
-        }
-        __syncthreads();
-        if (on) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (j < nj) buf_s[(w * 8 + g + j * ng) * kLinHS + e] = acc[j];
-        }
-        __syncthreads();
-    }
+    lin_stage_h(buf_s, a.theta + (size_t)b * P * NE, a.psid + bt * P, NE, P, t0, tend);
 
     // ---- solve: 8 lanes per symbol, lane a = column a.  Lanes past NT and groups past the chunk
     // repeat a valid column (no divergence around the cross-lane moves) and store nothing.
@@ -129,70 +74,13 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
     const bool mmse = a.kind == SBCE_LINEAR_MMSE;
     const double rho = mmse ? s2 / a.es : 0.0;
 
-    cd c[NT + 1];
-#pragma unroll
-    for (int i = 0; i <= NT; ++i) c[i] = czero();
-    for (int r = 0; r < NR; ++r) {
-        const cd ha = Hs[aa * NR + r];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) c[i] = cfmac(c[i], ha, Hs[i * NR + r]);   // conj(H[r][i]) H[r][a]
-        c[NT] = cfmac(c[NT], ha, a.yd[sym * NR + r]);                          // conj((H^H y)_a)
-    }
-    double diag = 0.0;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        const bool d = i == aa;
-        c[i].x = d ? c[i].x + rho : c[i].x;
-        diag = d ? c[i].x : diag;
-    }
-    const double tol = 1e-14 * group8_max(diag);
-
-    cd wv[NT];                       // forward substitution L w = e_a, in place
-#pragma unroll
-    for (int i = 0; i < NT; ++i) wv[i] = cmk(i == aa ? 1.0 : 0.0, 0.0);
-    bool fail = false;
-    double g = 0.0;
-    cd z = czero();
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int addr = ((lane & 56) | j) << 2;
-        const double piv = bperm_d(c[j].x, addr);
-        fail = fail || !(piv > tol);
-        const double rinv = fast_rsqrt64(piv);
-        cd lj[NT + 1];
-        cd laj = czero();
-#pragma unroll
-        for (int i = j + 1; i <= NT; ++i) {
-            lj[i] = cscale(bperm_c(c[i], addr), rinv);
-            if (i < NT) laj = csel(i == aa, lj[i], laj);
-        }
-        const cd wj = cscale(wv[j], rinv);
-        g = fma(wj.x, wj.x, g);
-        g = fma(wj.y, wj.y, g);
-        z = cfmac(z, cconj(wj), lj[NT]);                // conj(w_j) u_j, u_j = conj(lj[NT])
-#pragma unroll
-        for (int i = j + 1; i <= NT; ++i) {
-            c[i] = cfmac(c[i], cmk(-lj[i].x, -lj[i].y), laj);
-            if (i < NT) wv[i] = cfma(wv[i], cmk(-lj[i].x, -lj[i].y), wj);
-        }
-    }
-
-    cd xs = z;
-    double nu = s2 * g;
-    bool dead = false;
-    if (mmse) {
-        const double mu = fma(-rho, g, 1.0);
-        const double rmu = 1.0 / mu;
-        xs = cscale(z, rmu);
-        nu *= rmu;
-        dead = !(mu > 0.0);                             // a stream the channel does not carry
-    }
-    dead = dead || fail;                                // fail alone flags the trial
-    if (dead) {
-        xs = czero();
-        nu = INFINITY;
-    }
-    const double inv = dead ? 0.0 : 1.0 / nu;
+    double g;
+    cd z;
+    bool fail;
+    lin_solve<NT>(Hs, a.yd + sym * NR, NR, aa, lane, rho, g, z, fail);
+    cd xs;
+    double nu, inv;
+    lin_estimate(mmse, rho, s2, g, z, fail, xs, nu, inv);
 
     // ---- demap of stream a
     double dmin = INFINITY;

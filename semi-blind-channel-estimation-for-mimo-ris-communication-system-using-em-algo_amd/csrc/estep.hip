@@ -2697,6 +2697,7 @@ int estep_prep_stride(const Problem& pb) {
 }
 
 bool estep_supported(const Problem& pb, int mode) {
+    if (estep_linear_mode(mode)) return estep_linear_supported(pb, mode);
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return estep_pm_supported(pb, pb.pr, mode);
     Geometry g;
     return (mode == SBCE_ESTEP_SOFT || mode == SBCE_ESTEP_HARD) && make_geometry(pb, g);
@@ -2705,7 +2706,8 @@ bool estep_supported(const Problem& pb, int mode) {
 // The moment writers of launch_estep that fold EstepArgs::mchg: the tree pass's single-path store,
 // the enumeration, the n_tx = 4 factorised-weight pass and the MFMA sweep (listed or not) -- every
 // writer of a soft / hard E-step that takes the sweep branch below at n_tx >= 3.  Not the VALU
-// kernel, the n_tx = 2 factorised passes (estep_pair.hip) or the PM / ZF / MMSE / Gauss kernels.
+// kernel, the n_tx = 2 factorised passes (estep_pair.hip), the PM / ZF / MMSE / Gauss kernels or
+// the soft ZF / MMSE kernel (estep_linear.hip).
 bool estep_momfold_supported(const Problem& pb, int mode) {
     if (mode != SBCE_ESTEP_SOFT && mode != SBCE_ESTEP_HARD) return false;
     MfmaConst mc;
@@ -2715,6 +2717,7 @@ bool estep_momfold_supported(const Problem& pb, int mode) {
 }
 
 hipError_t launch_estep(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s) {
+    if (estep_linear_mode(mode)) return launch_estep_linear(pb, a, mode, s);
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return launch_estep_pm(pb, a, mode, pb.pr, s);
     const bool force_valu = g_debug.estep_valu;     // VALU kernel (A/B runs)
     MfmaConst mc;

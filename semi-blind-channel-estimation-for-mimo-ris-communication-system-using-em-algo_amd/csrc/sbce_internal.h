@@ -504,6 +504,10 @@ hipError_t launch_estep_pm(const Problem& pb, const EstepArgs& a, int mode, int 
                            hipStream_t s);
 bool estep_pm_supported(const Problem& pb, int partition_r, int mode);
 bool estep_supported(const Problem& pb, int mode);
+// soft ZF / MMSE E-step (estep_linear.hip): SBCE_ESTEP_MMSE_SOFT, SBCE_ESTEP_ZF_SOFT
+bool estep_linear_mode(int mode);
+bool estep_linear_supported(const Problem& pb, int mode);   // n_tx, n_rx 1..8, M a power of two <= 64
+hipError_t launch_estep_linear(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s);
 int estep_prep_stride(const Problem& pb);   // doubles per symbol, 0 if no MFMA sweep
 // pilots_factored: launch_pilot_factor already ran for these u_p (ppsi, pS, pflag valid)
 hipError_t launch_mstep_build(const Problem& pb, const MstepArgs& a, hipStream_t s,

@@ -19,7 +19,9 @@ def main():
     ap.add_argument("--monte-iter", type=int, default=15)
     ap.add_argument("--M", type=int, default=4)
     ap.add_argument("--estimators", nargs="+",
-                    default=["pilot", "soft", "hard", "pm", "zf", "mmse", "genie"])
+                    default=["pilot", "soft", "hard", "pm", "zf", "mmse", "genie"],
+                    help="pilot, genie, or an EM mode: soft hard pm pm_soft zf mmse (n_tx <= 8 "
+                         "but soft / hard: <= 4) and the soft mmse_soft zf_soft (n_tx <= 8)")
     ap.add_argument("--power", type=float, default=10.0)
     ap.add_argument("--noise", choices=["em", "true"], default="em")
     ap.add_argument("--seed", type=int, default=0)

@@ -20,6 +20,8 @@ Reference operator -> entry point here:
                                PM_beta.py:42-112 (posterior list weights) -> em_pm_soft()
   em_zf / em_mmse(..., h_initial, h)
                                all_detectorsvsTd.py:98-133 / :54-96      -> em_zf(), em_mmse()
+  (no reference counterpart)   the same argument list, soft per-stream ZF / MMSE posteriors
+                               on the clean channel, n_tx up to 8   -> em_zf_soft(), em_mmse_soft()
   EM_Gaussian_proposed(y_d, y_p, T_d, T_p, z_p, PsiTilde_td, varn, itera, H_initial, varx, n_tx)
                                MIMO_Gaussian_proposed.py:56-89 (Gaussian prior)
                                                                         -> EM_Gaussian_proposed()
@@ -66,7 +68,8 @@ def _dev(torch, arr, dtype=None):
 
 _MODES = {"soft": _lib.SBCE_ESTEP_SOFT, "hard": _lib.SBCE_ESTEP_HARD, "pm": _lib.SBCE_ESTEP_PM,
           "pm_soft": _lib.SBCE_ESTEP_PM_SOFT, "zf": _lib.SBCE_ESTEP_ZF,
-          "mmse": _lib.SBCE_ESTEP_MMSE, "gauss": _lib.SBCE_ESTEP_GAUSS}
+          "mmse": _lib.SBCE_ESTEP_MMSE, "gauss": _lib.SBCE_ESTEP_GAUSS,
+          "mmse_soft": _lib.SBCE_ESTEP_MMSE_SOFT, "zf_soft": _lib.SBCE_ESTEP_ZF_SOFT}
 _SOLVES = {"chol": _lib.SBCE_SOLVE_CHOL, "drop": _lib.SBCE_SOLVE_CHOL_DROP,
            "lstsq": _lib.SBCE_SOLVE_MINNORM}
 
@@ -179,8 +182,11 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
       cons (M,), theta0 (B,K) with K = P*n_tx*n_rx.
     Optional: x_d_true (B,T_d,n_tx) -> per-iteration LLF (IterationsvsLLF.py:76);
     h_true (B,K) -> the reference's oracle early stop (PM.py:110-112).
-    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse"; partition_r selects the PM
-    list size.  return_decisions (hard modes): x_dest (B,T_d,n_tx), the last E-step's
+    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft";
+    partition_r selects the PM list size.  "mmse_soft" / "zf_soft": the soft E-step for up to 8
+    streams -- per-stream MMSE / ZF equalisation on the clean channel and a Gaussian soft demapper
+    (detect_linear_batch's moments, include/sbce.h SBCE_ESTEP_MMSE_SOFT); "zf_soft" needs
+    n_rx >= n_tx, neither takes x_sup or return_decisions.  return_decisions (hard modes): x_dest (B,T_d,n_tx), the last E-step's
     decisions (SER/log_max_SER.py:77-78).  x_sup (B,T_d,n_tx): pilot symbols superimposed
     on the data (Parallel/ParallelProtocol_Tp.py:63-86), soft/hard modes.  mode "gauss":
     Gaussian-prior EM (MIMO_Gaussian_proposed.py:56-89) with prior variance parameter varx;
@@ -210,7 +216,7 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
     return _result(torch, out, return_device)
 
 
-_NOISE_MODES = ("soft", "hard", "pm", "pm_soft", "zf", "mmse")
+_NOISE_MODES = ("soft", "hard", "pm", "pm_soft", "zf", "mmse", "mmse_soft", "zf_soft")
 
 
 def _noise_checks(mode, varn_min):
@@ -270,8 +276,8 @@ def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft",
     theta, on the device, inside the iteration chain -- per iteration E-step, M-step, noise update
     (csrc/noise.hip), oracle early stop.  ``varn`` (one value or (B,)) is only the START of the
     parameter; the posterior of every E-step divides by the current estimate squared, sigma^2.
-    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse".  varn_min: floor of the parameter (a
-    trial that reaches it has SBCE_STATUS_NOISE set and varn == varn_min exactly).
+    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft".  varn_min:
+    floor of the parameter (a trial that reaches it has SBCE_STATUS_NOISE set and varn == varn_min exactly).
     Returns dict(theta (B,K), varn (B,) the parameter after each trial's last update, sigma2 =
     varn**2, hist (B,itera) the parameter after each iteration (a stopped trial's later entries
     hold its last value), status (B,), iters_done (B,)).
@@ -329,7 +335,8 @@ def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta
     skipped by every later launch.  estimate_noise: the noise parameter is estimated beside theta
     as in em_batch_noise (``varn`` is then only its start).  loglik=True records the
     log-likelihood after every iteration (one sbce_loglik pass each: a diagnostic, soft-EM shapes
-    with n_tx <= 4 and M**n_tx <= 65536 only).
+    with n_tx <= 4 and M**n_tx <= 65536 only).  mode: as em_batch_noise ("mmse_soft" / "zf_soft"
+    included: the theta rule works at every n_tx, loglik=True keeps its n_tx <= 4 limit).
     Returns dict(theta (B,K), iters_done (B,), status (B,) with SBCE_STATUS_CONVERGED where a rule
     stopped the trial, dtheta_hist (B,max_iters) the relative step after each iteration, ll_hist
     (B,max_iters) or None, varn (B,) the parameter each trial ended with, sigma2 = varn**2, hist
@@ -536,6 +543,45 @@ def em_mmse(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, 
     Z_d and is never returned; it is not part of the result.)"""
     return _detector(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
                      h_initial, h, "mmse", solve, verbose)
+
+
+def _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_initial, h, mode,
+                 solve, verbose):
+    """_detector for the soft ZF / MMSE modes: all_possibleSymbols may also be the (M,) table
+    itself (the M^n_tx hypothesis table is never enumerated and is out of reach at n_tx = 8);
+    n_tx then follows from h_initial's length."""
+    aps = np.asarray(aps)
+    if aps.ndim != 1:
+        return _detector(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_initial, h,
+                         mode, solve, verbose)
+    Psi = np.asarray(PsiTilde_td)[:, :T_d]
+    n_tx = np.asarray(h_initial).size // (Psi.shape[0] * np.asarray(Y_d[0]).shape[0])
+    d = _prepare_single(Y_d[:T_d], Y_p[:T_p], Z_p[:T_p], Psi, None, M, h_initial, n_tx=n_tx,
+                        cons=aps[:int(M)])
+    hh = None if h is None else np.asarray(h, dtype=complex).reshape(1, -1)
+    res = em_batch(d["y_d"], d["y_p"], d["psi_d"], d["u_p"], d["cons"], varn, itera, d["theta0"],
+                   mode=mode, h_true=hh, solve=solve)
+    return _finish(res, verbose, itera)
+
+
+def em_zf_soft(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
+               h_initial, h, verbose=False, solve="chol"):
+    """Soft zero-forcing EM for up to 8 streams (em_zf's argument list; n_rx >= n_tx): per symbol
+    z = (H^H H)^{-1} H^H y on the clean effective channel, per-stream noise variance
+    varn^2 (H^H H)^{-1}_aa, and the posterior moments of a Gaussian soft demapper per stream
+    (include/sbce.h SBCE_ESTEP_ZF_SOFT) instead of em_zf's one-hot decision.  ``h`` drives the
+    oracle early stop when given.  A symbol whose H^H H is singular carries the uniform
+    posterior and flags the trial SBCE_STATUS_DETECTOR (last_status)."""
+    return _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
+                        h_initial, h, "zf_soft", solve, verbose)
+
+
+def em_mmse_soft(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
+                 h_initial, h, verbose=False, solve="chol"):
+    """Soft MMSE EM for up to 8 streams (em_mmse's argument list): the unbiased LMMSE estimate
+    with A = H^H H + (varn^2 / mean |cons|^2) I, otherwise as em_zf_soft (SBCE_ESTEP_MMSE_SOFT)."""
+    return _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
+                        h_initial, h, "mmse_soft", solve, verbose)
 
 
 def em_ml_ser(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
@@ -960,7 +1006,8 @@ def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0,
                 workspace=True, return_status=False):
     """One device E-step (sbce_estep): returns m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx) and, with
     return_status, the (B,) status words (SBCE_STATUS_DETECTOR: a ZF / MMSE decision past the
-    hypothesis table).  varn may be one value or one per trial ((B,), as em_batch takes it).
+    hypothesis table, or a failed pivot of a symbol in "mmse_soft" / "zf_soft").  mode: any of
+    em_batch's.  varn may be one value or one per trial ((B,), as em_batch takes it).
     workspace=False passes no workspace (the exact sweep then prepares each symbol in
     its own kernel instead of the separate preparation pass)."""
     torch = _torch()

@@ -21,7 +21,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--partition-r", type=int, default=1)
     ap.add_argument("--detectors", nargs="+", default=None,
-                    help="subset of pm_soft hard zf mmse soft (default: all five)")
+                    help="subset of pm_soft hard zf mmse soft (default: all five), or the soft "
+                         "E-steps for up to 8 streams: mmse_soft zf_soft")
     ap.add_argument("--no-replay", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -29,7 +30,7 @@ def main():
     pkg = package()
     x, curves = pkg.sweeps.nmse_vs_snr(tuple(a.SNR), a.T_d, a.T_p, a.N, a.n_rx, a.n_tx, a.itera,
                                        a.monte_iter, a.M, a.power, a.seed, replay=not a.no_replay,
-                                       modes=tuple(a.detectors or pkg.sweeps.SNR_DETECTORS),
+                                       modes=tuple(a.detectors or pkg.sweeps.SNR_DEFAULT_MODES),
                                        partition_r=a.partition_r)
     labels = {k: v[2] for k, v in pkg.sweeps.SNR_DETECTORS.items()}
     report("SNR", x, {labels[k]: v for k, v in curves.items()}, a.out,
