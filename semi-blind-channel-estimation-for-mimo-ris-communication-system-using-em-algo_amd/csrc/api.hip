@@ -22,8 +22,6 @@ namespace sbce {
 DebugConfig g_debug;
 
 namespace {
-constexpr int kSphereBudgetMax = 256;      // estep.hip kBfsPmax
-
 void read_debug_env(DebugConfig& c) {
     c = kDebugDefault;
     auto env = [](const char* n) { const char* v = getenv(n); return (v && v[0]) ? v : nullptr; };
@@ -35,7 +33,7 @@ void read_debug_env(DebugConfig& c) {
     if ((v = env("SBCE_ESTEP_SPHERE"))) c.estep_nosphere = v[0] == '0';
     if ((v = env("SBCE_SPHERE_BUDGET"))) {
         const int bu = atoi(v);
-        c.sphere_budget = bu < 1 ? 1 : (bu > kSphereBudgetMax ? kSphereBudgetMax : bu);
+        c.sphere_budget = bu < 1 ? 1 : (bu > kBfsPmax ? kBfsPmax : bu);
     }
     if ((v = env("SBCE_BACKSUB"))) c.backsub_general = v[0] == '1';
     if ((v = env("SBCE_CHOL_IMPL"))) c.chol_valu = v[0] == 'v';

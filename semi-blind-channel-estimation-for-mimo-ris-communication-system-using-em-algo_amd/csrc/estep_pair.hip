@@ -1,6 +1,6 @@
 // Exact soft E-step by factorised weights, for the cfg-1 geometry (n_tx = 4, 16-QAM) symbols
 // the sphere pass leaves to the tile sweep because their posterior is wide (low SNR, early EM
-// iterations).  Same posterior as estep.hip:
+// iterations).  Same posterior as estep_valu.hip:
 // "Proposed method/Proposed_method_NMSEvsTp.py":61-71, beta = exp(-||y - Z theta||^2/varn^2)/sum.
 //
 // The log-weight of hypothesis x = (x0, x1, x2, x3) with H_eff = [h_0 .. h_3],
@@ -22,7 +22,7 @@
 // D <= kPairDmax every weight within e^-50 of the maximum is a normal double (> e^-700) and no
 // partial product overflows: the symbol is resolved here.  Otherwise (D grows like 1/varn^2:
 // high SNR) the sweep weighs it.  The enumeration routes a symbol here only when the tree pass's
-// upper bound of D (estep.hip pair_screen, tree record word 31) is within the limit, so the exact
+// upper bound of D (estep_sphere.hip pair_screen, tree record word 31) is within the limit, so the exact
 // test below is a safety net (a failing symbol would join the sweep's list).
 #include "sbce_internal.h"
 
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
 // WAVE per symbol, lane = (a0, b0): 288 exponentials and ~100 VALU ops per lane plus eleven wave
 // sums instead of 4096 distances and exponentials.  Range as above: the largest weight is
 // >= exp(-D), D = (sum of the eight table maxima) - l(x_c); the tree pass routes a symbol here
-// only when its D (estep.hip fact2_bound) is within kPairDmax, and a symbol whose sum Z still
+// only when its D (estep_sphere.hip fact2_bound) is within kPairDmax, and a symbol whose sum Z still
 // leaves the normal range joins the sweep's list.
 constexpr int kF2Waves = 4;
 
@@ -813,7 +813,7 @@ hipError_t launch_estep_pair(const Problem& pb, const EstepArgs& a, int stride, 
     PairConst c;
     c.B = pb.B; c.Td = pb.Td; c.stride = stride;
     c.inv_s2 = 1.0 / (pb.varn * pb.varn);
-    c.thr_d = 50.0 * pb.varn * pb.varn;              // estep.hip kSkipThr varn^2 (TrialNoise::thr_d)
+    c.thr_d = kSkipThr * pb.varn * pb.varn;          // TrialNoise::thr_d
     c.count = count;
     // waves grab listed symbols until the list is exhausted: a grid that fills the chip
     const long nsym = (long)pb.B * pb.Td;

@@ -11,8 +11,9 @@
 // lane l of the wave owns the rows q = 64 qb + l and loops over s; the residual
 // y - sum_{a<NT-1} H[:,a] x_a is formed once per row, each distance costs NR complex FMAs.
 //
-// Not for the E-step units (estep.hip, estep_pair.hip, estep_pm.hip): they are compiled without
-// NaN honouring and their effective-channel sums have their own orders.
+// Not for the E-step units (estep_valu.hip, estep_sweep.hip, estep_sphere.hip, estep_pair.hip,
+// estep_pm.hip): they are compiled without NaN honouring and their effective-channel sums have
+// their own orders.
 #pragma once
 #include "sbce_internal.h"
 

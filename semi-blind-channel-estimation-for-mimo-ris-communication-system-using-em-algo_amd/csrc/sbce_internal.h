@@ -341,16 +341,18 @@ __device__ __forceinline__ void mom_store(cd* p, const cd& v, bool arm, unsigned
     *p = v;
 }
 
+// The exact E-steps skip weights below e^-kSkipThr of the running posterior maximum
+constexpr double kSkipThr = 50.0;
 // The posterior constants of one noise variance v, in the operation order of the host's scalar
 // path (the launchers' 1 / (varn varn), kSkipThr varn varn, 0.1 varn varn), so that a trial with
-// varn_t[b] == dims.varn gets bitwise the constants of a scalar call.  kSkipThr = 50 (estep.hip).
+// varn_t[b] == dims.varn gets bitwise the constants of a scalar call.
 struct TrialNoise {
     double inv_s2, thr_d, reg, s2;
 };
 __device__ __forceinline__ TrialNoise trial_noise(double v) {
     TrialNoise n;
     n.inv_s2 = 1.0 / (v * v);
-    n.thr_d = 50.0 * v * v;
+    n.thr_d = kSkipThr * v * v;
     n.reg = 0.1 * v * v;
     n.s2 = v * v;
     return n;
@@ -399,6 +401,9 @@ __device__ inline void grid_build(const cd* cons, int M, GridLds* g) {
 
 constexpr int kTreeRecDoubles = 32;   // (word 31: the factorised-weight pass's screen)
 constexpr int kEstepListCnt = 16;      // int32 counters after the sweep's list
+// path list capacity per level of the sphere pass's enumeration (estep_bfs_kernel's LDS lists);
+// DebugConfig::sphere_budget is clamped to it
+constexpr int kBfsPmax = 256;
 // the factorised-weight pass (estep_pair.hip) takes a symbol whose range D is at most this
 constexpr double kPairDmax = 640.0;
 
@@ -499,7 +504,49 @@ struct TileExt {
     int fwd;
 };
 
+// Exact (soft / hard) E-step, estep.hip: the routing over the three units below.
 hipError_t launch_estep(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s);
+// The hypothesis split both exact E-step geometries start from: streams A = {0 .. NT/2 - 1} and
+// B = the rest, JA = M^|A| and JB = M^|B| hypotheses each.  False: n_tx not 1..4, n_rx not 1..8,
+// M no power of two in 2..64, or more than 2^24 hypotheses.
+struct HypSplit {
+    int lm;            // log2(M)
+    long JA, JB;
+};
+inline bool hyp_split(const Problem& pb, HypSplit& h) {
+    if (pb.NT < 1 || pb.NT > 4 || pb.NR < 1 || pb.NR > 8) return false;
+    if (pb.M < 2 || pb.M > 64 || (pb.M & (pb.M - 1))) return false;
+    h.lm = 0;
+    while ((1 << h.lm) < pb.M) ++h.lm;
+    const int NA = pb.NT / 2, NB = pb.NT - NA;
+    h.JA = 1L << (h.lm * NA);
+    h.JB = 1L << (h.lm * NB);
+    return h.JA * h.JB <= (1L << 24);
+}
+// VALU kernel (estep_valu.hip): every supported shape; the route where no sweep exists
+bool estep_valu_supported(const Problem& pb);
+hipError_t launch_estep_valu(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s);
+// MFMA sweep (estep_sweep.hip).  What the passes in front of it and the router need of its
+// geometry: the one source of these numbers (the per-symbol passes must see the sweep's bits).
+struct SweepPlan {
+    bool ok;           // a sweep exists for the shape (false: every other field is 0)
+    int lm, JB;
+    int prep_stride;   // doubles per symbol of EstepArgs::prep
+    int count;         // SBCE_ESTEP_COUNT=1
+    double reg;        // 0.1 varn^2
+    double inv_s2, thr_d;
+    long blocks;       // grid of the unlisted sweep
+};
+SweepPlan estep_sweep_plan(const Problem& pb);
+hipError_t launch_estep_sweep(const Problem& pb, const EstepArgs& a, int mode, long blocks,
+                              hipStream_t s);
+// The one-thread-per-symbol passes that feed the sweep through EstepArgs::prep (estep_sphere.hip):
+// the preparation pass, or the sphere pass (tree, enumeration or estep_pair.hip's passes, bounds
+// of the listed symbols; a.list and a.tree set, n_rx >= n_tx)
+hipError_t launch_estep_prep(const Problem& pb, const EstepArgs& a, const SweepPlan& sp, int mode,
+                             hipStream_t s);
+hipError_t launch_estep_sphere(const Problem& pb, const EstepArgs& a, const SweepPlan& sp, int mode,
+                               hipStream_t s);
 hipError_t launch_estep_pm(const Problem& pb, const EstepArgs& a, int mode, int partition_r,
                            hipStream_t s);
 bool estep_pm_supported(const Problem& pb, int partition_r, int mode);

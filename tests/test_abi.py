@@ -52,6 +52,20 @@ def test_product_library_has_no_switches_and_ab_build_has_same_abi(sbce):
     assert ab.sbce_debug_reload_env() == 0         # no switch set here: defaults
 
 
+def test_build_lists_every_unit():
+    """__graft_entry__.SOURCES is exactly the set of csrc/*.hip and every UNIT_FLAGS key is one of
+    them: a unit left out of the build, or flags keyed to a unit that was renamed, fails here
+    and not at link time (no library is loaded, nothing is compiled)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("sbce_graft_entry",
+                                                  os.path.join(ROOT, "__graft_entry__.py"))
+    entry = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(entry)
+    units = sorted(f for f in os.listdir(entry.CSRC) if f.endswith(".hip"))
+    assert sorted(entry.SOURCES) == units
+    assert set(entry.UNIT_FLAGS) <= set(entry.SOURCES), set(entry.UNIT_FLAGS) - set(entry.SOURCES)
+
+
 def test_struct_layout_matches_c(sbce, tmp_path):
     """Compile a probe against include/sbce.h with gcc and compare sizes/offsets."""
     probe = tmp_path / "probe.c"

@@ -1,5 +1,5 @@
 """The per-group bounds T_3 / T_1 of the V16 sweep as tools/e0_group_bounds.py restates them
-(csrc/estep.hip build_tri: one stream relaxed, tables rounded to float32, the device's margins):
+(csrc/estep_sweep.hip build_tri: one stream relaxed, tables rounded to float32, the device's margins):
 the bound less its margin never exceeds the exact minimum of its tile group, and the sweep with
 its running minimum never skips a group that holds a hypothesis inside the final threshold."""
 import os

@@ -1,4 +1,4 @@
-"""The V16 sweep's per-group bounds T_3 / T_1 (csrc/estep.hip build_tri, SBCE_ESTEP_TRI in the
+"""The V16 sweep's per-group bounds T_3 / T_1 (csrc/estep_sweep.hip build_tri, SBCE_ESTEP_TRI in the
 A/B build: 0 off, 1 built once 4 groups of a symbol reached the screen -- the default -- and 2
 built for every swept symbol).
 

@@ -5,7 +5,7 @@ generator signal_model.synthetic_batch, no device and no library) of the V16 E-s
 cons[tg .. tg+3], every x_1 and x_3 -- survive the column-tile bound (P-perp of span(h_0, h_1)),
 the row-tile bound (P-perp of span(h_1, h_3)) and the per-group bounds T_3 / T_1 (one stream
 relaxed) and reach the FP32 screen, and which pass it to the FP64 MFMAs.  Natural sweep order,
-the running minimum starting at the ridge-rounded candidate, the device's constants (csrc/estep.hip:
+the running minimum starting at the ridge-rounded candidate, the device's constants (csrc/estep_sweep.hip:
 threshold 50 varn^2, ridge 0.1 varn^2, the margins of lb_margin, the screen and build_tri; the
 per-group tables rounded to float32 as the device forms them).
 
@@ -18,7 +18,7 @@ import sys
 
 import numpy as np
 
-THR, RIDGE = 50.0, 0.1          # kSkipThr, MfmaConst::reg (both times varn^2)
+THR, RIDGE = 50.0, 0.1          # kSkipThr (csrc/sbce_internal.h), MfmaConst::reg (both times varn^2)
 GATE = 4                        # kTriGate
 
 
