@@ -114,6 +114,39 @@ extern "C" {
                                    n_tx; ll_hist keeps sbce_loglik's own n_tx <= 4 limit).
                                    Deterministic: trial b of a B-trial call is bitwise the B = 1
                                    call, varn_t[b] == dims.varn gives the scalar call's bits */
+/* value 9 is not a mode (SBCE_EUNSUPPORTED) */
+#define SBCE_ESTEP_EP 10        /* expectation-propagation E-step for n_tx = 1..8 (an additive
+                                   extension of ABI 7; Cespedes et al., "Expectation Propagation
+                                   Detection for High-Order High-Dimensional MIMO Systems", IEEE
+                                   Trans. Commun. 2014): p passes of the MMSE_SOFT solve, each with
+                                   the per-stream posterior means and variances of the pass before
+                                   as a Gaussian prior.  Per (b, t), with H, s2 and es as for
+                                   MMSE_SOFT, G = H^H H, u = H^H y and per stream a the state r_a
+                                   (real), q_a (complex), starting at r_a = s2 / es, q_a = 0; pass
+                                   l = 1..p:
+                                     A = G + diag(r) by Cholesky (same pivot rule);
+                                     g_a = (A^-1)_aa, z = A^-1 (u + q);
+                                     mu_a = 1 - r_a g_a, h2_a = s2 g_a / mu_a (cavity variance),
+                                     t_a = (z_a - g_a q_a) / mu_a (cavity mean);
+                                     post[a][s] ~ e^{-|t_a - cons[s]|^2 / h2_a},
+                                     m_a = sum_s post cons, s_a = sum_s post |cons|^2;
+                                     unless l = p: v_a = max(s_a - |m_a|^2, 5e-7 es),
+                                     r' = s2 (1/v_a - 1/h2_a), q' = s2 (m_a/v_a - t_a/h2_a) and, when
+                                     r' is finite and > 0, r_a <- (r' + r_a) / 2, q_a <- (q' + q_a) / 2
+                                     (damping 0.5; otherwise both keep their values).
+                                   Pass 1 is MMSE_SOFT.  Moments of the last pass in MMSE_SOFT's
+                                   product form: m_a, S[a][a] = s_a, S[a][c] = m_a conj(m_c).
+                                   dims.partition_r carries p: 0 gives the default 5, 1..16 are
+                                   taken as given, above 16: SBCE_EINVAL.
+                                   Degenerate cases: a failed pivot in any pass gives the whole
+                                   symbol the uniform posterior's moments and sets
+                                   SBCE_STATUS_DETECTOR; a stream with mu_a <= 0 in a pass gets the
+                                   uniform posterior for itself in that pass and keeps its r and q.
+                                   Every output is finite for any s2 > 0.
+                                   Limits, errors, entry points and determinism are MMSE_SOFT's
+                                   (n_tx, n_rx 1..8, m a power of two in 2..64, else
+                                   SBCE_EUNSUPPORTED; x_dest or x_sup: SBCE_EINVAL); every sum's
+                                   order is fixed by (n_tx, n_rx, n_psi, m, p) */
 
 /* M-step solve modes (SURVEY.md §7 hard part 3) */
 #define SBCE_SOLVE_CHOL 0       /* Hermitian Cholesky of the reduced L x L system
@@ -147,7 +180,8 @@ extern "C" {
 #define SBCE_STATUS_DETECTOR 4  /* ZF/MMSE: the reference's flattened argmin indexed past
                                    all_possibleSymbols (IndexError at
                                    all_detectorsvsTd.py:52); row flat mod M^n_tx used.
-                                   ZF_SOFT / MMSE_SOFT: a symbol's A = H^H H + rho I had a pivot
+                                   ZF_SOFT / MMSE_SOFT / EP: a symbol's A = H^H H + rho I (EP:
+                                   G + diag(r) of some pass) had a pivot
                                    <= 1e-14 max_a A_aa; that symbol carries the uniform
                                    posterior's moments (NONHPD stays the M-step's finding about R
                                    in the chain's status word) */
@@ -170,7 +204,8 @@ typedef struct sbce_dims {
     int32_t t_d;        /* data symbols */
     int32_t m;          /* constellation size (power of two, 2..64) */
     int32_t partition_r;/* PM modes: list = M^(p+1) with p = int(partition_r /
-                           log2 M) (PM.py:74), at most 64 members; else 0 */
+                           log2 M) (PM.py:74), at most 64 members; SBCE_ESTEP_EP: the pass
+                           count (0 = 5, 1..16); else 0 */
     double varn;        /* noise variance parameter; posterior uses varn^2 */
     double varx;        /* SBCE_ESTEP_GAUSS only: symbol variance parameter, the prior
                            covariance uses varx^2 (MIMO_Gaussian_proposed.py:44); else ignored */
@@ -449,7 +484,7 @@ int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
 /* sbce_em with the noise parameter estimated: varn_est[b] starts at p->varn_t[b] (or d->varn) and
  * is the E-step's per-trial parameter; per iteration E-step, M-step, noise update, then the oracle
  * early stop (p->h_true), so a trial's last M-step is followed by its update.  p->workspace as for
- * sbce_em.  estep_mode: SOFT, HARD, PM, PM_SOFT, ZF, MMSE, MMSE_SOFT, ZF_SOFT; SBCE_ESTEP_GAUSS gives
+ * sbce_em.  estep_mode: SOFT, HARD, PM, PM_SOFT, ZF, MMSE, MMSE_SOFT, ZF_SOFT, EP; SBCE_ESTEP_GAUSS gives
  * SBCE_EUNSUPPORTED (its S_t is not a second moment).  Decided before any HIP call, beside
  * sbce_em's own checks -- SBCE_EINVAL: p->x_sup or p->llf set, null or misaligned (8 bytes)
  * varn_est, varn_hist or scratch, varn_min <= 0, flags != 0; SBCE_EWORKSPACE: scratch_bytes too
@@ -548,6 +583,18 @@ int sbce_em_conv(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mo
  *   moments [B][T_d][n_tx + n_tx^2] complex    status [B] int32 */
 #define SBCE_LINEAR_MMSE 0
 #define SBCE_LINEAR_ZF 1
+/* kind 2 is not a kind (SBCE_EINVAL) */
+#define SBCE_LINEAR_EP 3        /* expectation propagation, the passes of SBCE_ESTEP_EP (above) with
+                                   s2 = sigma2 and the caller's es (> 0): x_soft = t and nu = h2 of
+                                   the last pass -- the extrinsic estimate of each stream and its
+                                   variance -- and idx_hat, x_hat, post, llr, err and moments follow
+                                   from them exactly as they follow from (x_soft, nu) of MMSE.  A
+                                   failed pivot in any pass gives the symbol x_soft = 0, nu = +inf
+                                   and the trial SBCE_STATUS_NONHPD; a stream with mu_a <= 0 in the
+                                   last pass gets the same outputs for itself alone */
+/* flags bits 8..15 of SBCE_LINEAR_EP: the pass count, 0 = the default 5, 1..16; above 16:
+ * SBCE_EINVAL.  For the other kinds these bits are unknown bits. */
+#define SBCE_LINEAR_EP_PASSES(n) (((n) & 0xff) << 8)
 
 typedef struct sbce_linear_dims {
     int32_t batch;      /* B: independent trials (>= 1) */
@@ -557,9 +604,9 @@ typedef struct sbce_linear_dims {
     int32_t t_d;        /* data symbols (>= 1) */
     int32_t m;          /* table size (power of two, 2..64) */
     int32_t kind;       /* SBCE_LINEAR_* */
-    int32_t flags;      /* SBCE_DETECT_MAXLOG; every other bit 0 */
+    int32_t flags;      /* SBCE_DETECT_MAXLOG, SBCE_LINEAR_EP_PASSES(n) (EP); every other bit 0 */
     double sigma2;      /* > 0: the denominator itself, as sbce_detect_dims.sigma2 */
-    double es;          /* > 0: symbol energy of the MMSE prior (mean |cons|^2; 1 gives the
+    double es;          /* > 0: symbol energy of the MMSE / EP prior (mean |cons|^2; 1 gives the
                            reference's filter of all_detectorsvsTd.py:71); ignored by ZF */
 } sbce_linear_dims;
 
@@ -592,7 +639,7 @@ int sbce_detect_linear_workspace_bytes(const sbce_linear_dims* d, size_t* bytes)
  * kernel nodes only), then one kernel launch, in this order on `hip_stream`; no allocation, no
  * synchronisation, no floating-point atomic; capturable in a HIP graph.
  * Decided before any HIP call -- SBCE_EINVAL: null dims / ptrs / required pointer, batch, t_d,
- * n_psi, n_tx or n_rx < 1, m not a power of two in 2..64, sigma2 <= 0, MMSE with es <= 0, an
+ * n_psi, n_tx or n_rx < 1, m not a power of two in 2..64, sigma2 <= 0, MMSE or EP with es <= 0, an
  * unknown kind or flag bit, llr without labels, err without x_d_true or labels, ZF with
  * n_rx < n_tx, a misaligned pointer (16 bytes complex, 8 float64, 4 int32);
  * SBCE_EUNSUPPORTED: n_tx > 8 or n_rx > 8; SBCE_EWORKSPACE. */

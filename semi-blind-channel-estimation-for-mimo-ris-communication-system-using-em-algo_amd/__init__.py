@@ -10,7 +10,7 @@ from . import sweeps  # noqa: F401
 from ._lib import SbceUnavailable, SbceError  # noqa: F401
 from .em import (  # noqa: F401
     em, em_ml, em_llf, em_ml_llf, em_ml_ser, em_pm, em_pm_soft, em_zf, em_mmse, em_superimposed,
-    em_zf_soft, em_mmse_soft,
+    em_zf_soft, em_mmse_soft, em_ep,
     em_zero_init, em_batch, ser_batch, estep_batch,
     mstep_batch, nmse_batch, EMEngine, EM_Gaussian_proposed, gauss_expand_batch,
     gaussian_regressors, reduce_gaussian_channel, em_approx_batch, EM_approx,
@@ -19,7 +19,7 @@ from .em import (  # noqa: F401
 )
 
 __all__ = ["em", "em_ml", "em_llf", "em_ml_llf", "em_ml_ser", "em_pm", "em_pm_soft", "em_zf",
-           "em_mmse", "em_zf_soft", "em_mmse_soft", "em_superimposed", "ser_batch", "EM_Gaussian_proposed", "gauss_expand_batch",
+           "em_mmse", "em_zf_soft", "em_mmse_soft", "em_ep", "em_superimposed", "ser_batch", "EM_Gaussian_proposed", "gauss_expand_batch",
            "em_zero_init", "em_batch", "em_approx_batch", "EM_approx",
            "detect_batch", "detect", "em_batch_noise", "noise_var_batch",
            "loglik_batch", "em_batch_conv", "detect_linear_batch", "detect_linear",

@@ -24,6 +24,7 @@ SBCE_ESTEP_MMSE = 5
 SBCE_ESTEP_GAUSS = 6
 SBCE_ESTEP_MMSE_SOFT = 7
 SBCE_ESTEP_ZF_SOFT = 8
+SBCE_ESTEP_EP = 10
 SBCE_SOLVE_CHOL = 0
 SBCE_SOLVE_CHOL_DROP = 1
 SBCE_SOLVE_MINNORM = 2
@@ -38,6 +39,14 @@ SBCE_STATUS_CONVERGED = 128
 SBCE_DETECT_MAXLOG = 1
 SBCE_LINEAR_MMSE = 0
 SBCE_LINEAR_ZF = 1
+SBCE_LINEAR_EP = 3
+SBCE_EP_MAX_PASSES = 16     # csrc/sbce_internal.h kEpMaxPasses
+
+
+def linear_ep_passes(n):
+    """SBCE_LINEAR_EP_PASSES(n): the EP pass count in sbce_linear_dims.flags bits 8..15."""
+    return (int(n) & 0xff) << 8
+
 
 EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_workspace_bytes_solve", "sbce_em", "sbce_em_multi",

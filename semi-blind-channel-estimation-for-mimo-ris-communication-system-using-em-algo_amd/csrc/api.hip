@@ -207,12 +207,17 @@ MstepArgs mstep_args(const Problem& pb, const sbce_ptrs* p, const void* moments,
     return ma;
 }
 
-// SBCE_ESTEP_MMSE_SOFT / ZF_SOFT report n_tx or n_rx past 8 as SBCE_EUNSUPPORTED, like
+// SBCE_ESTEP_MMSE_SOFT / ZF_SOFT / EP report n_tx or n_rx past 8 as SBCE_EUNSUPPORTED, like
 // sbce_detect_linear, whose arithmetic they are (include/sbce.h); make_problem alone would say
 // SBCE_EINVAL, which stays the answer for every other mode.
 bool linear_oversize(const sbce_dims* d, int estep_mode) {
-    return d && estep_linear_mode(estep_mode) && d->n_tx >= 1 && d->n_rx >= 1 &&
+    return d && (estep_linear_mode(estep_mode) || estep_mode == SBCE_ESTEP_EP) && d->n_tx >= 1 && d->n_rx >= 1 &&
            (d->n_tx > 8 || d->n_rx > 8);
+}
+
+// SBCE_ESTEP_EP reads partition_r as its pass count: 0 (the default) .. 16
+bool ep_passes_invalid(const Problem& pb, int estep_mode) {
+    return estep_mode == SBCE_ESTEP_EP && ep_passes_of(pb.pr) < 0;
 }
 
 // The E-step's arguments: moments out, and the MFMA sweep's regions of the workspace carved by
@@ -407,6 +412,7 @@ struct EmChain {
         s = (hipStream_t)hip_stream;
         if (linear_oversize(d, estep_mode)) return SBCE_EUNSUPPORTED;
         if (!make_problem(d, pb) || iters < 0) return SBCE_EINVAL;
+        if (ep_passes_invalid(pb, estep_mode)) return SBCE_EINVAL;
         if ((nz || cv) && estep_mode == SBCE_ESTEP_GAUSS) return SBCE_EUNSUPPORTED;
         if (!estep_supported(pb, estep_mode) || !chol_supported(pb)) return SBCE_EUNSUPPORTED;
         if (!valid_solve(solve_mode)) return SBCE_EINVAL;
@@ -847,6 +853,7 @@ int sbce_estep(const sbce_dims* d, const sbce_ptrs* p, int estep_mode, void* mom
     Problem pb;
     if (linear_oversize(d, estep_mode)) return SBCE_EUNSUPPORTED;
     if (!make_problem(d, pb)) return SBCE_EINVAL;
+    if (ep_passes_invalid(pb, estep_mode)) return SBCE_EINVAL;
     int rc = check_ptrs(p, pb, false);
     if (rc) return rc;
     if (!moments || !aligned16(moments)) return SBCE_EINVAL;
@@ -1144,10 +1151,16 @@ int sbce_detect_linear_workspace_bytes(const sbce_linear_dims* d, size_t* bytes)
 int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, void* hip_stream) {
     if (!d || !p) return SBCE_EINVAL;
     if (d->batch < 1 || d->n_tx < 1 || d->n_rx < 1 || d->n_psi < 1 || d->t_d < 1 ||
-        !(d->sigma2 > 0.0) || (d->flags & ~SBCE_DETECT_MAXLOG))
+        !(d->sigma2 > 0.0))
         return SBCE_EINVAL;
-    if (d->kind != SBCE_LINEAR_MMSE && d->kind != SBCE_LINEAR_ZF) return SBCE_EINVAL;
-    if (d->kind == SBCE_LINEAR_MMSE && !(d->es > 0.0)) return SBCE_EINVAL;
+    if (d->kind != SBCE_LINEAR_MMSE && d->kind != SBCE_LINEAR_ZF && d->kind != SBCE_LINEAR_EP)
+        return SBCE_EINVAL;
+    // flags bits 8..15 carry the EP pass count (0: the default, 1..16); unknown bits for MMSE / ZF
+    const int known = SBCE_DETECT_MAXLOG | (d->kind == SBCE_LINEAR_EP ? 0xff00 : 0);
+    if (d->flags & ~known) return SBCE_EINVAL;
+    const int ep_word = (d->flags >> 8) & 0xff;
+    if (d->kind == SBCE_LINEAR_EP && ep_passes_of(ep_word) < 0) return SBCE_EINVAL;
+    if (d->kind != SBCE_LINEAR_ZF && !(d->es > 0.0)) return SBCE_EINVAL;
     if (d->m < 2 || d->m > 64 || (d->m & (d->m - 1))) return SBCE_EINVAL;   // a power of two
     if (!required({p->y_d, p->psi_d, p->cons, p->theta})) return SBCE_EINVAL;
     if ((p->llr || p->err) && !p->labels) return SBCE_EINVAL;
@@ -1177,6 +1190,7 @@ int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, voi
     a.B = d->batch; a.NT = d->n_tx; a.NR = d->n_rx; a.P = d->n_psi; a.Td = d->t_d; a.M = d->m;
     a.kind = d->kind;
     a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0;
+    a.passes = ep_passes_of(ep_word);
     a.sigma2 = d->sigma2; a.es = d->es;
     return hip_rc(launch_detect_linear(a, (hipStream_t)hip_stream));
 }

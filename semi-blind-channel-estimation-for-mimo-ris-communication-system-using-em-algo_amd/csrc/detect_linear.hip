@@ -31,13 +31,19 @@
 // workgroup reads another's results: trial b of a B-trial call is bitwise the B = 1 call.
 // Launches: one small kernel that zeroes err and status (when either is set), then the detection
 // kernel: a linear chain of two kernel nodes on the caller's stream, no memset node.
-#include "linear_solve.h"
+//
+// SBCE_LINEAR_EP (the EP instantiation of the kernel): the solve and the estimate are replaced by
+// the passes of ep_solve.h on the same staged H, and x_soft = t, nu = h2 are the cavity mean and
+// variance of the last pass; everything after them is the same code.  The MMSE / ZF instantiation
+// keeps its statements in their former order and LinearArgs its former offsets (the new field is
+// last): its instructions are those of the kernel before the EP flag.
+#include "ep_solve.h"
 
 namespace sbce {
 
 namespace {
 
-template <int NT>
+template <int NT, bool EP>
 __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a) {
     __shared__ cd buf_s[kLinBuf];
     __shared__ cd cons_s[64];
@@ -77,10 +83,16 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
     double g;
     cd z;
     bool fail;
-    lin_solve<NT>(Hs, a.yd + sym * NR, NR, aa, lane, rho, g, z, fail);
+    if constexpr (!EP) lin_solve<NT>(Hs, a.yd + sym * NR, NR, aa, lane, rho, g, z, fail);
     cd xs;
     double nu, inv;
-    lin_estimate(mmse, rho, s2, g, z, fail, xs, nu, inv);
+    if constexpr (!EP) {
+        lin_estimate(mmse, rho, s2, g, z, fail, xs, nu, inv);
+    } else {
+        cd c0[NT + 1];
+        ep_gram<NT>(Hs, a.yd + sym * NR, NR, aa, c0);
+        ep_run<NT>(c0, cons_s, M, s2, a.es, a.passes, aa, lane, xs, nu, inv, fail);
+    }
 
     // ---- demap of stream a
     double dmin = INFINITY;
@@ -199,8 +211,12 @@ __global__ __launch_bounds__(256) void linear_zero_kernel(int32_t* err, int32_t*
 
 template <int NT>
 hipError_t launch_nt(const LinearArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(detect_linear_kernel<NT>, dim3((unsigned)(a.B * a.chunks)), dim3(kLinThreads),
-                       0, s, a);
+    if (a.kind == SBCE_LINEAR_EP)
+        hipLaunchKernelGGL((detect_linear_kernel<NT, true>), dim3((unsigned)(a.B * a.chunks)),
+                           dim3(kLinThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL((detect_linear_kernel<NT, false>), dim3((unsigned)(a.B * a.chunks)),
+                           dim3(kLinThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // E-step routing: which unit computes the per-symbol posterior moments of (pb, mode).
 //   soft ZF / MMSE                 estep_linear.hip
+//   expectation propagation        estep_ep.hip
 //   PM / ZF / MMSE / Gauss         estep_pm.hip
 //   exact soft / hard              the MFMA sweep (estep_sweep.hip) where one exists for the shape
 //                                  (JA, JB >= 16), behind the preparation or the sphere pass
@@ -11,6 +12,7 @@ namespace sbce {
 
 bool estep_supported(const Problem& pb, int mode) {
     if (estep_linear_mode(mode)) return estep_linear_supported(pb, mode);
+    if (mode == SBCE_ESTEP_EP) return estep_ep_supported(pb);
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return estep_pm_supported(pb, pb.pr, mode);
     return (mode == SBCE_ESTEP_SOFT || mode == SBCE_ESTEP_HARD) && estep_valu_supported(pb);
 }
@@ -19,7 +21,7 @@ bool estep_supported(const Problem& pb, int mode) {
 // the enumeration, the n_tx = 4 factorised-weight pass and the MFMA sweep (listed or not) -- every
 // writer of a soft / hard E-step that takes the sweep branch below at n_tx >= 3.  Not the VALU
 // kernel, the n_tx = 2 factorised passes (estep_pair.hip), the PM / ZF / MMSE / Gauss kernels or
-// the soft ZF / MMSE kernel (estep_linear.hip).
+// the soft ZF / MMSE and EP kernels (estep_linear.hip, estep_ep.hip).
 bool estep_momfold_supported(const Problem& pb, int mode) {
     if (mode != SBCE_ESTEP_SOFT && mode != SBCE_ESTEP_HARD) return false;
     return !g_debug.estep_valu && pb.NT >= 3 && estep_sweep_plan(pb).ok;
@@ -27,6 +29,7 @@ bool estep_momfold_supported(const Problem& pb, int mode) {
 
 hipError_t launch_estep(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s) {
     if (estep_linear_mode(mode)) return launch_estep_linear(pb, a, mode, s);
+    if (mode == SBCE_ESTEP_EP) return launch_estep_ep(pb, a, s);
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return launch_estep_pm(pb, a, mode, pb.pr, s);
     const SweepPlan sp = estep_sweep_plan(pb);
     // SBCE_ESTEP_IMPL=valu: the VALU kernel at every shape (A/B runs)

@@ -283,7 +283,7 @@ bool debug_nondefault();   // a result-affecting switch differs from its default
 // ------------------------------------------------------------------ launch API
 struct Problem {
     int B, NT, NR, P, Tp, Td, M, L, K;
-    int pr;            // partition_r (PM E-step modes)
+    int pr;            // partition_r (PM E-step modes; SBCE_ESTEP_EP: the pass count)
     double varn;
     double varx;       // Gaussian-prior E-step (SBCE_ESTEP_GAUSS)
 };
@@ -555,6 +555,18 @@ bool estep_supported(const Problem& pb, int mode);
 bool estep_linear_mode(int mode);
 bool estep_linear_supported(const Problem& pb, int mode);   // n_tx, n_rx 1..8, M a power of two <= 64
 hipError_t launch_estep_linear(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s);
+
+// expectation-propagation E-step (estep_ep.hip): SBCE_ESTEP_EP, pb.pr = the pass count (0: default)
+constexpr int kEpDefaultPasses = 5;
+constexpr int kEpMaxPasses = 16;
+// the pass count of a caller's word (dims.partition_r, or flags bits 8..15 of the linear detector):
+// 0 = the default, 1..kEpMaxPasses as given, -1 for anything else
+inline int ep_passes_of(int word) {
+    if (word == 0) return kEpDefaultPasses;
+    return word >= 1 && word <= kEpMaxPasses ? word : -1;
+}
+bool estep_ep_supported(const Problem& pb);   // the soft MMSE E-step's limits, pr in 0..16
+hipError_t launch_estep_ep(const Problem& pb, const EstepArgs& a, hipStream_t s);
 int estep_prep_stride(const Problem& pb);   // doubles per symbol, 0 if no MFMA sweep
 // pilots_factored: launch_pilot_factor already ran for these u_p (ppsi, pS, pflag valid)
 hipError_t launch_mstep_build(const Problem& pb, const MstepArgs& a, hipStream_t s,
@@ -699,6 +711,7 @@ struct LinearArgs {
     int kind;          // SBCE_LINEAR_*
     int maxlog;        // llr holds the max-log L-values
     double sigma2, es;
+    int passes;        // SBCE_LINEAR_EP: EP passes (1..16); last, so that no earlier field moves
 };
 bool detect_linear_supported(int NT, int NR);   // 1..8, 1..8
 hipError_t launch_detect_linear(LinearArgs a, hipStream_t s);

@@ -21,14 +21,15 @@ def main():
     ap.add_argument("--estimators", nargs="+",
                     default=["pilot", "soft", "hard", "pm", "zf", "mmse", "genie"],
                     help="pilot, genie, or an EM mode: soft hard pm pm_soft zf mmse (n_tx <= 8 "
-                         "but soft / hard: <= 4) and the soft mmse_soft zf_soft (n_tx <= 8)")
+                         "but soft / hard: <= 4) and the soft mmse_soft zf_soft ep (n_tx <= 8)")
     ap.add_argument("--power", type=float, default=10.0)
     ap.add_argument("--noise", choices=["em", "true"], default="em")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-replay", action="store_true")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--detector", choices=["ml", "mmse", "zf"], default="ml",
-                    help="joint ML (n_tx <= 4) or per-stream LMMSE / ZF soft detection (n_tx <= 8)")
+    ap.add_argument("--detector", choices=["ml", "mmse", "zf", "ep"], default="ml",
+                    help="joint ML (n_tx <= 4) or per-stream LMMSE / ZF / expectation-propagation "
+                         "soft detection (n_tx <= 8)")
     a = ap.parse_args()
     init_distributed()
     pkg = package()
@@ -38,7 +39,7 @@ def main():
         detector=a.detector)
     curves = {f"SER {e}": v for e, v in ser.items()}
     curves.update({f"BER {e}": v for e, v in ber.items()})
-    title = {"ml": "ML", "mmse": "LMMSE", "zf": "ZF"}[a.detector]
+    title = {"ml": "ML", "mmse": "LMMSE", "zf": "ZF", "ep": "EP"}[a.detector]
     report("SNR", x, curves, a.out, f"{title} detection per channel estimate", ylabel="error rate",
            logy=True)
     report("SNR", x, {f"NMSE {e}": v for e, v in nmse.items()})

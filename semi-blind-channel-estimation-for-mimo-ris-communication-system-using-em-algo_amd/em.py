@@ -22,6 +22,7 @@ Reference operator -> entry point here:
                                all_detectorsvsTd.py:98-133 / :54-96      -> em_zf(), em_mmse()
   (no reference counterpart)   the same argument list, soft per-stream ZF / MMSE posteriors
                                on the clean channel, n_tx up to 8   -> em_zf_soft(), em_mmse_soft()
+  expectation propagation (EP), n_tx up to 8                        -> em_ep()
   EM_Gaussian_proposed(y_d, y_p, T_d, T_p, z_p, PsiTilde_td, varn, itera, H_initial, varx, n_tx)
                                MIMO_Gaussian_proposed.py:56-89 (Gaussian prior)
                                                                         -> EM_Gaussian_proposed()
@@ -69,9 +70,23 @@ def _dev(torch, arr, dtype=None):
 _MODES = {"soft": _lib.SBCE_ESTEP_SOFT, "hard": _lib.SBCE_ESTEP_HARD, "pm": _lib.SBCE_ESTEP_PM,
           "pm_soft": _lib.SBCE_ESTEP_PM_SOFT, "zf": _lib.SBCE_ESTEP_ZF,
           "mmse": _lib.SBCE_ESTEP_MMSE, "gauss": _lib.SBCE_ESTEP_GAUSS,
-          "mmse_soft": _lib.SBCE_ESTEP_MMSE_SOFT, "zf_soft": _lib.SBCE_ESTEP_ZF_SOFT}
+          "mmse_soft": _lib.SBCE_ESTEP_MMSE_SOFT, "zf_soft": _lib.SBCE_ESTEP_ZF_SOFT,
+          "ep": _lib.SBCE_ESTEP_EP}
 _SOLVES = {"chol": _lib.SBCE_SOLVE_CHOL, "drop": _lib.SBCE_SOLVE_CHOL_DROP,
            "lstsq": _lib.SBCE_SOLVE_MINNORM}
+
+
+def _mode_word(mode, partition_r, ep_passes):
+    """dims.partition_r of a call: the PM list parameter, or for mode "ep" the pass count
+    (include/sbce.h SBCE_ESTEP_EP: None / 0 = the default 5, else 1..16)."""
+    if mode != "ep":
+        if ep_passes is not None:
+            raise ValueError("ep_passes needs mode 'ep'")
+        return int(partition_r)
+    n = 0 if ep_passes is None else int(ep_passes)
+    if not 0 <= n <= _lib.SBCE_EP_MAX_PASSES:
+        raise ValueError(f"ep_passes must be 0 (the default) .. {_lib.SBCE_EP_MAX_PASSES}")
+    return n
 
 
 def _varn_arg(torch, varn, B):
@@ -173,7 +188,7 @@ def _result(torch, out, return_device):
 
 def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_true=None,
              h_true=None, solve="chol", return_device=False, partition_r=0,
-             return_decisions=False, x_sup=None, varx=1.0):
+             return_decisions=False, x_sup=None, varx=1.0, ep_passes=None):
     """Run ``itera`` EM iterations on a batch of independent trials.
 
     Array layouts (complex128, batch-major, include/sbce.h):
@@ -182,11 +197,14 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
       cons (M,), theta0 (B,K) with K = P*n_tx*n_rx.
     Optional: x_d_true (B,T_d,n_tx) -> per-iteration LLF (IterationsvsLLF.py:76);
     h_true (B,K) -> the reference's oracle early stop (PM.py:110-112).
-    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft";
+    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft" | "ep";
     partition_r selects the PM list size.  "mmse_soft" / "zf_soft": the soft E-step for up to 8
     streams -- per-stream MMSE / ZF equalisation on the clean channel and a Gaussian soft demapper
     (detect_linear_batch's moments, include/sbce.h SBCE_ESTEP_MMSE_SOFT); "zf_soft" needs
-    n_rx >= n_tx, neither takes x_sup or return_decisions.  return_decisions (hard modes): x_dest (B,T_d,n_tx), the last E-step's
+    n_rx >= n_tx, neither takes x_sup or return_decisions.  "ep": expectation propagation
+    (SBCE_ESTEP_EP), ``ep_passes`` passes (None: 5; 1..16) of the "mmse_soft" solve, each with the
+    demapper's per-stream means and variances of the pass before as the prior; limits as
+    "mmse_soft".  return_decisions (hard modes): x_dest (B,T_d,n_tx), the last E-step's
     decisions (SER/log_max_SER.py:77-78).  x_sup (B,T_d,n_tx): pilot symbols superimposed
     on the data (Parallel/ParallelProtocol_Tp.py:63-86), soft/hard modes.  mode "gauss":
     Gaussian-prior EM (MIMO_Gaussian_proposed.py:56-89) with prior variance parameter varx;
@@ -199,7 +217,8 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
     """
     torch = _torch()
     lib = _lib.load()
-    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn, partition_r, varx,
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn,
+                 _mode_word(mode, partition_r, ep_passes), varx,
                  solve=_SOLVES[solve], check="theta0", clone=True)
     Xd, Ht, Xs = (_cdev(torch, x) for x in (x_d_true, h_true, x_sup))
     llf = (torch.zeros((st.B, max(itera, 1)), dtype=torch.float64, device="cuda")
@@ -216,7 +235,7 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
     return _result(torch, out, return_device)
 
 
-_NOISE_MODES = ("soft", "hard", "pm", "pm_soft", "zf", "mmse", "mmse_soft", "zf_soft")
+_NOISE_MODES = ("soft", "hard", "pm", "pm_soft", "zf", "mmse", "mmse_soft", "zf_soft", "ep")
 
 
 def _noise_checks(mode, varn_min):
@@ -271,12 +290,13 @@ def noise_var_batch(y_d, y_p, psi_d, u_p, theta, m, S, varn_min=1e-6, return_sta
 
 
 def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", solve="chol",
-                   partition_r=0, h_true=None, varn_min=1e-6, return_device=False):
+                   partition_r=0, h_true=None, varn_min=1e-6, return_device=False, ep_passes=None):
     """em_batch with the noise parameter unknown (sbce_em_noise): it is estimated per trial beside
     theta, on the device, inside the iteration chain -- per iteration E-step, M-step, noise update
     (csrc/noise.hip), oracle early stop.  ``varn`` (one value or (B,)) is only the START of the
     parameter; the posterior of every E-step divides by the current estimate squared, sigma^2.
-    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft".  varn_min:
+    mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft" | "ep"
+    (with ``ep_passes``, as em_batch).  varn_min:
     floor of the parameter (a trial that reaches it has SBCE_STATUS_NOISE set and varn == varn_min exactly).
     Returns dict(theta (B,K), varn (B,) the parameter after each trial's last update, sigma2 =
     varn**2, hist (B,itera) the parameter after each iteration (a stopped trial's later entries
@@ -289,7 +309,8 @@ def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft",
         raise ValueError("itera must be >= 1")
     torch = _torch()
     lib = _lib.load()
-    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn, partition_r,
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn,
+                 _mode_word(mode, partition_r, ep_passes),
                  solve=_SOLVES[solve], check="theta0", clone=True)
     opts, est, hist, scratch = _noise_opts(torch, lib, st, vmin, int(itera))
     Ht = _cdev(torch, h_true)
@@ -327,7 +348,7 @@ def loglik_batch(y_d, y_p, psi_d, u_p, cons, theta, varn, n_tx, per_symbol=False
 
 def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta=1e-6, tol_ll=0.0,
                   min_iters=2, estimate_noise=False, varn_min=1e-6, loglik=False, mode="soft",
-                  partition_r=0, solve="chol", return_device=False):
+                  partition_r=0, solve="chol", return_device=False, ep_passes=None):
     """em_batch with a per-trial stop that needs no ground truth (sbce_em_conv): a trial stops
     after iteration l (at least min_iters performed) when ||theta_l - theta_{l-1}|| <= tol_theta
     ||theta_l|| (theta_{-1} = theta0), or -- tol_ll > 0, which needs loglik=True -- when its
@@ -335,7 +356,7 @@ def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta
     skipped by every later launch.  estimate_noise: the noise parameter is estimated beside theta
     as in em_batch_noise (``varn`` is then only its start).  loglik=True records the
     log-likelihood after every iteration (one sbce_loglik pass each: a diagnostic, soft-EM shapes
-    with n_tx <= 4 and M**n_tx <= 65536 only).  mode: as em_batch_noise ("mmse_soft" / "zf_soft"
+    with n_tx <= 4 and M**n_tx <= 65536 only).  mode: as em_batch_noise ("mmse_soft" / "zf_soft" / "ep"
     included: the theta rule works at every n_tx, loglik=True keeps its n_tx <= 4 limit).
     Returns dict(theta (B,K), iters_done (B,), status (B,) with SBCE_STATUS_CONVERGED where a rule
     stopped the trial, dtheta_hist (B,max_iters) the relative step after each iteration, ll_hist
@@ -357,7 +378,8 @@ def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta
     vmin = _noise_checks(mode, varn_min)
     torch = _torch()
     lib = _lib.load()
-    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn, partition_r,
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta0, varn,
+                 _mode_word(mode, partition_r, ep_passes),
                  solve=_SOLVES[solve], check="theta0", clone=True)
     B = st.B
     dth = torch.zeros((B, iters), dtype=torch.float64, device="cuda")
@@ -546,21 +568,24 @@ def em_mmse(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, 
 
 
 def _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_initial, h, mode,
-                 solve, verbose):
+                 solve, verbose, ep_passes=None):
     """_detector for the soft ZF / MMSE modes: all_possibleSymbols may also be the (M,) table
     itself (the M^n_tx hypothesis table is never enumerated and is out of reach at n_tx = 8);
     n_tx then follows from h_initial's length."""
     aps = np.asarray(aps)
-    if aps.ndim != 1:
-        return _detector(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_initial, h,
-                         mode, solve, verbose)
     Psi = np.asarray(PsiTilde_td)[:, :T_d]
-    n_tx = np.asarray(h_initial).size // (Psi.shape[0] * np.asarray(Y_d[0]).shape[0])
-    d = _prepare_single(Y_d[:T_d], Y_p[:T_p], Z_p[:T_p], Psi, None, M, h_initial, n_tx=n_tx,
-                        cons=aps[:int(M)])
+    if aps.ndim != 1:
+        if mode != "ep":
+            return _detector(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_initial,
+                             h, mode, solve, verbose)
+        d = _prepare_single(Y_d[:T_d], Y_p[:T_p], Z_p[:T_p], Psi, aps, M, h_initial)
+    else:
+        n_tx = np.asarray(h_initial).size // (Psi.shape[0] * np.asarray(Y_d[0]).shape[0])
+        d = _prepare_single(Y_d[:T_d], Y_p[:T_p], Z_p[:T_p], Psi, None, M, h_initial, n_tx=n_tx,
+                            cons=aps[:int(M)])
     hh = None if h is None else np.asarray(h, dtype=complex).reshape(1, -1)
     res = em_batch(d["y_d"], d["y_p"], d["psi_d"], d["u_p"], d["cons"], varn, itera, d["theta0"],
-                   mode=mode, h_true=hh, solve=solve)
+                   mode=mode, h_true=hh, solve=solve, ep_passes=ep_passes)
     return _finish(res, verbose, itera)
 
 
@@ -582,6 +607,16 @@ def em_mmse_soft(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, v
     with A = H^H H + (varn^2 / mean |cons|^2) I, otherwise as em_zf_soft (SBCE_ESTEP_MMSE_SOFT)."""
     return _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
                         h_initial, h, "mmse_soft", solve, verbose)
+
+
+def em_ep(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera, h_initial, h,
+          verbose=False, solve="chol", ep_passes=None):
+    """Expectation-propagation EM for up to 8 streams (em_mmse_soft's argument list): ``ep_passes``
+    passes (None: 5; 1..16) of em_mmse_soft's solve per symbol, each with the demapper's
+    per-stream means and variances of the pass before as the prior (include/sbce.h
+    SBCE_ESTEP_EP); one pass is em_mmse_soft."""
+    return _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
+                        h_initial, h, "ep", solve, verbose, ep_passes)
 
 
 def em_ml_ser(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
@@ -874,19 +909,26 @@ def detect(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, labels=None, X
 
 _WANT_LINEAR = ("x_soft", "nu", "x_hat", "idx", "llr", "post")
 _WANT_LINEAR_ALL = _WANT_LINEAR + ("moments", "status")
-_LINEAR_KINDS = {"mmse": _lib.SBCE_LINEAR_MMSE, "zf": _lib.SBCE_LINEAR_ZF}
+_LINEAR_KINDS = {"mmse": _lib.SBCE_LINEAR_MMSE, "zf": _lib.SBCE_LINEAR_ZF,
+                 "ep": _lib.SBCE_LINEAR_EP}
 
 
 def _detect_linear_call(torch, Yd, Ps, Cs, Th, n_tx, kind, sigma2, sigma2_t, es, lab, Xd, maxlog,
-                        want):
+                        want, ep_passes=None):
     """One sbce_detect_linear on device tensors; returns the dict of device outputs."""
     lib = _lib.load()
     B, T_d, n_rx = Yd.shape
     P, M = Ps.shape[2], Cs.shape[0]
     if Ps.shape != (B, T_d, P) or Th.shape != (B, P * n_tx * n_rx):
         raise ValueError("detect_linear: inconsistent shapes")
+    if isinstance(kind, tuple):                        # ("ep", passes)
+        if len(kind) != 2 or ep_passes is not None:
+            raise ValueError("kind must be a name or ('ep', passes), the passes given once")
+        kind, ep_passes = kind
     if kind not in _LINEAR_KINDS:
-        raise ValueError("kind must be 'mmse' or 'zf'")
+        raise ValueError("kind must be 'mmse', 'zf' or 'ep'")
+    flags = (_lib.SBCE_DETECT_MAXLOG if maxlog else 0) | _lib.linear_ep_passes(
+        _mode_word(kind, 0, ep_passes))
     lgM = max(int(M - 1).bit_length(), 1)
     bad = set(want) - set(_WANT_LINEAR_ALL)
     if bad:
@@ -904,8 +946,8 @@ def _detect_linear_call(torch, Yd, Ps, Cs, Th, n_tx, kind, sigma2, sigma2_t, es,
     def ptr(k):
         return out[k].data_ptr() if k in out else None
 
-    dims = _lib.LinearDims(B, n_tx, n_rx, P, T_d, M, _LINEAR_KINDS[kind],
-                           _lib.SBCE_DETECT_MAXLOG if maxlog else 0, float(sigma2), float(es))
+    dims = _lib.LinearDims(B, n_tx, n_rx, P, T_d, M, _LINEAR_KINDS[kind], flags, float(sigma2),
+                           float(es))
     nb = ctypes.c_size_t(0)
     _lib.check(lib.sbce_detect_linear_workspace_bytes(ctypes.byref(dims), ctypes.byref(nb)),
                "sbce_detect_linear_workspace_bytes")
@@ -940,7 +982,9 @@ def detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind="mmse", es=Non
 
     Arguments as detect_batch.  kind: 'mmse' (LMMSE equaliser with the prior energy ``es``; None
     means mean |cons|^2, 1 gives the reference's filter of all_detectorsvsTd.py:71) or 'zf' (needs
-    n_rx >= n_tx).  Returns a dict with the outputs named in ``want``: x_soft (B,T_d,n_tx) the
+    n_rx >= n_tx) or 'ep' (expectation propagation, SBCE_LINEAR_EP: 5 passes of the 'mmse' solve,
+    or ('ep', p) for p = 1..16 passes; x_soft and nu are then the extrinsic estimate and variance
+    of the last pass).  Returns a dict with the outputs named in ``want``: x_soft (B,T_d,n_tx) the
     unbiased per-stream estimate and nu its effective noise variance; x_hat / idx the per-stream
     nearest table point; post (B,T_d,n_tx,M) and llr (B,T_d,n_tx,log2 M) of the Gaussian demapper
     (exact or, maxlog=True, max-log); moments (B,T_d,n_tx+n_tx^2) in estep_batch's layout; status
@@ -958,10 +1002,12 @@ def detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind="mmse", es=Non
 
 
 def detect_linear(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, kind="mmse", es=None,
-                  labels=None, X_d=None, noise="em", maxlog=False, want=_WANT_LINEAR):
+                  labels=None, X_d=None, noise="em", maxlog=False, want=_WANT_LINEAR,
+                  ep_passes=None):
     """detect_linear_batch for one trial in the reference's list layouts (as detect()).
     all_possibleSymbols may also be the (M,) table itself (the M^n_tx hypothesis table is never
     enumerated here and is out of reach at n_tx = 8); n_tx then follows from theta's length.
+    ep_passes: the pass count of kind 'ep' (None: 5), as kind=('ep', ep_passes).
     Returns the dict of detect_linear_batch without the batch axis."""
     aps = np.asarray(all_possibleSymbols)
     T_d = len(Y_d)
@@ -975,8 +1021,8 @@ def detect_linear(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, kind="m
         cons = cons_from_aps(aps, int(M))
     xt = None if X_d is None else np.stack([np.asarray(x).reshape(-1) for x in X_d[:T_d]])[None]
     r = detect_linear_batch(y, psi, cons, np.asarray(theta, dtype=complex).reshape(1, -1), varn,
-                            n_tx, kind=kind, es=es, labels=labels, x_d_true=xt, noise=noise,
-                            maxlog=maxlog, want=want)
+                            n_tx, kind=kind if ep_passes is None else (kind, ep_passes), es=es,
+                            labels=labels, x_d_true=xt, noise=noise, maxlog=maxlog, want=want)
     return {k: v[0] for k, v in r.items()}
 
 
@@ -1003,11 +1049,11 @@ def em_zero_init(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, v
 
 # ------------------------------------------------------------------ diagnostic stages
 def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0, varx=1.0,
-                workspace=True, return_status=False):
+                workspace=True, return_status=False, ep_passes=None):
     """One device E-step (sbce_estep): returns m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx) and, with
     return_status, the (B,) status words (SBCE_STATUS_DETECTOR: a ZF / MMSE decision past the
-    hypothesis table, or a failed pivot of a symbol in "mmse_soft" / "zf_soft").  mode: any of
-    em_batch's.  varn may be one value or one per trial ((B,), as em_batch takes it).
+    hypothesis table, or a failed pivot of a symbol in "mmse_soft" / "zf_soft" / "ep").  mode: any of
+    em_batch's ("ep" with ``ep_passes``).  varn may be one value or one per trial ((B,), as em_batch takes it).
     workspace=False passes no workspace (the exact sweep then prepares each symbol in
     its own kernel instead of the separate preparation pass)."""
     torch = _torch()
@@ -1016,7 +1062,8 @@ def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0,
     P = np.shape(psi_d)[2]
     y_p = np.zeros((B, 0, n_rx), dtype=complex)
     u_p = np.zeros((B, 0, P * n_tx), dtype=complex)
-    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta, varn, partition_r, varx,
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, theta, varn,
+                 _mode_word(mode, partition_r, ep_passes), varx,
                  check="theta" if np.ndim(varn) else None, workspace=workspace)
     mom = torch.zeros((B, T_d, n_tx + n_tx * n_tx), dtype=torch.complex128, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
@@ -1107,12 +1154,13 @@ class EMEngine:
     """
 
     def __init__(self, batch, varn, mode="soft", solve="chol", x_d_true=None, h_true=None,
-                 partition_r=0, varx=1.0, x_sup=None, streams=1, early_stop=False):
-        """early_stop=True: the reference's oracle early stop on the true channel (PM.py:110-112,
+                 partition_r=0, varx=1.0, x_sup=None, streams=1, early_stop=False, ep_passes=None):
+        """ep_passes: the pass count of mode "ep" (None: 5).  early_stop=True: the reference's oracle early stop on the true channel (PM.py:110-112,
         all_detectorsvsTd.py's five EMs) with h_true (or batch["h"]); ``iters_done`` then holds
         the iterations each trial of the last run() performed."""
         torch = _torch()
         self.torch = torch
+        partition_r = _mode_word(mode, partition_r, ep_passes)
         # varn: one noise variance, or one per trial (the SNR axis of a sweep batched into one
         # call).  The engine owns the workspace (below): the staged problem gets none of its own.
         st = _Staged(torch, batch["y_d"], batch["y_p"], batch["psi_d"], batch["u_p"], batch["cons"],
@@ -1256,7 +1304,7 @@ class EMEngine:
         return _result(torch, out, return_device)
 
     def detect_linear(self, kind="mmse", es=None, labels=None, x_d_true=None, noise="em",
-                      maxlog=False, want=_WANT_LINEAR, return_device=False):
+                      maxlog=False, want=_WANT_LINEAR, return_device=False, ep_passes=None):
         """One sbce_detect_linear on the engine's resident y_d, psi_d, cons and CURRENT theta, on
         the current stream: the outputs of detect_linear_batch (n_tx up to 8).  x_d_true defaults
         to the engine's own."""
@@ -1267,7 +1315,7 @@ class EMEngine:
         s2, s2t = _sigma2_arg(torch, (self.varn, self.varn_t), self.B, noise)
         out = _detect_linear_call(torch, self.y_d, self.psi_d, self.cons, self.theta, self.n_tx,
                                   kind, s2, s2t, self.es_table if es is None else float(es), lab_d,
-                                  xd, maxlog, tuple(want))
+                                  xd, maxlog, tuple(want), ep_passes)
         return _result(torch, out, return_device)
 
     def nmse(self):

@@ -22,7 +22,7 @@ def main():
     ap.add_argument("--partition-r", type=int, default=1)
     ap.add_argument("--detectors", nargs="+", default=None,
                     help="subset of pm_soft hard zf mmse soft (default: all five), or the soft "
-                         "E-steps for up to 8 streams: mmse_soft zf_soft")
+                         "E-steps for up to 8 streams: mmse_soft zf_soft ep")
     ap.add_argument("--no-replay", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()

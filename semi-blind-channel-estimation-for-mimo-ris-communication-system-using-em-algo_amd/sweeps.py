@@ -203,6 +203,8 @@ SNR_DETECTORS = {
     # selectable by name, not part of the default figure
     "mmse_soft": ("soft MMSE (no reference counterpart)", False, "Soft MMSE"),
     "zf_soft": ("soft ZF (no reference counterpart)", False, "Soft ZF"),
+    # expectation propagation on the soft MMSE solve (em.em_ep), default pass count
+    "ep": ("expectation propagation (no reference counterpart)", False, "EP"),
 }
 # the reference figure's five EMs: the default of nmse_vs_snr
 SNR_DEFAULT_MODES = ("pm_soft", "hard", "zf", "mmse", "soft")
@@ -230,8 +232,8 @@ def nmse_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2
     """Mean NMSE per SNR of the five EMs of PMd/SNR/all_Detectors.py (driver :362-395; varn =
     power / 10^(SNR/10), :351-354): em_pm (r = 1), em_ml, em_zf, em_mmse and the exact em, each
     with that script's own early-stop pattern (SNR_DETECTORS) and np.linalg.solve M-step.
-    modes may also name "mmse_soft" / "zf_soft" (the soft E-steps for n_tx up to 8, which the
-    reference does not have); pm_soft, zf and mmse take n_tx up to 8 too, hard and soft up to 4.
+    modes may also name "mmse_soft" / "zf_soft" / "ep" (the soft E-steps for n_tx up to 8, which
+    the reference does not have); pm_soft, zf and mmse take n_tx up to 8 too, hard and soft up to 4.
 
     One batched sbce_em per detector over this rank's trials of EVERY SNR point (per-trial noise
     variances; batch_snr=False: one call per (SNR point, detector), the same results); the
@@ -420,24 +422,24 @@ def detection_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n
     """Uncoded SER and BER (and NMSE) per SNR of the joint ML detector (sbce_detect) fed each
     estimator's channel, on gen_snr's data (the layout of PMd/SNR/all_Detectors.py:362-370):
     'pilot' = the pilot-only start h0, 'genie' = the true h, every other name an em_batch mode
-    (soft, hard, pm, pm_soft, zf, mmse, mmse_soft, zf_soft) whose theta after ``itera`` iterations
+    (soft, hard, pm, pm_soft, zf, mmse, mmse_soft, zf_soft, ep) whose theta after ``itera`` iterations
     is used.  The SAME detector serves every estimator;
     per-trial symbol and bit error counts come from the device counters and are accumulated as
     extras, all-reduced ONCE with the NMSE sums.  noise: the detector's sigma^2 ('em' varn^2,
     'true' varn); labels: the bit labelling (default qam.gray_labeling).
-    detector: 'ml' (sbce_detect, n_tx <= 4), or the linear receivers 'mmse' / 'zf'
-    (sbce_detect_linear, prior energy mean |cons|^2), which take n_tx up to 8 with the estimators
-    pilot, genie, pm, pm_soft, zf, mmse, mmse_soft and zf_soft; soft and hard keep the exact
+    detector: 'ml' (sbce_detect, n_tx <= 4), or the linear receivers 'mmse' / 'zf' / 'ep'
+    (sbce_detect_linear, prior energy mean |cons|^2; 'ep' with its default pass count), which take
+    n_tx up to 8 with the estimators pilot, genie, pm, pm_soft, zf, mmse, mmse_soft, zf_soft and ep; soft and hard keep the exact
     E-step's own limit
     (n_tx <= 4, M^n_tx <= 2^24) and raise ValueError beyond it.
     Returns (SNR, ser {est: curve}, ber {est: curve}, nmse {est: curve})."""
     estimators = tuple(estimators)
     bad = [e for e in estimators if e not in ("pilot", "genie", "soft", "hard", "pm", "pm_soft",
-                                              "zf", "mmse", "mmse_soft", "zf_soft")]
+                                              "zf", "mmse", "mmse_soft", "zf_soft", "ep")]
     if bad:
         raise ValueError(f"unknown estimators {bad}")
-    if detector not in ("ml", "mmse", "zf"):
-        raise ValueError("detector must be 'ml', 'mmse' or 'zf'")
+    if detector not in ("ml", "mmse", "zf", "ep"):
+        raise ValueError("detector must be 'ml', 'mmse', 'zf' or 'ep'")
     if detector != "ml" and (n_tx > 4 or M ** n_tx > 1 << 24):
         beyond = [e for e in estimators if e in ("soft", "hard")]
         if beyond:
