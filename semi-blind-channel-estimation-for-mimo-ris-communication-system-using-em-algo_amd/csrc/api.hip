@@ -47,6 +47,7 @@ void read_debug_env(DebugConfig& c) {
     if ((v = env("SBCE_PM_IMPL"))) c.pm_impl = (v[0] == 'w' || v[0] == 't' || v[0] == 'q') ? v[0] : 0;
     if ((v = env("SBCE_SMALL_SOLVE"))) c.small_col = v[0] == 'c';
     if ((v = env("SBCE_ESTEP_TRI"))) c.estep_tri = (v[0] >= '0' && v[0] <= '2') ? v[0] - '0' : 1;
+    if ((v = env("SBCE_ESTEP_ORDER"))) c.estep_noorder = v[0] == '0';
     if ((v = env("SBCE_SMALL_STOP"))) c.small_stop = (v[0] >= '1' && v[0] <= '4') ? v[0] - '0' : 0;
 }
 
@@ -57,7 +58,7 @@ bool debug_nondefault() {
     const DebugConfig& c = g_debug;
     const DebugConfig& d = kDebugDefault;
     return c.estep_valu != d.estep_valu || c.estep_noprune != d.estep_noprune ||
-           c.estep_nof32 != d.estep_nof32 || c.estep_tri != d.estep_tri ||
+           c.estep_nof32 != d.estep_nof32 || c.estep_tri != d.estep_tri || c.estep_noorder != d.estep_noorder ||
            c.estep_nosphere != d.estep_nosphere || c.sphere_budget != d.sphere_budget ||
            c.backsub_general != d.backsub_general || c.chol_valu != d.chol_valu ||
            c.estep_nopair != d.estep_nopair || c.cplx3 != d.cplx3 ||

@@ -160,6 +160,8 @@ struct MfmaConst {
     int screen;                // V16 FP32 screen of the tile groups (SBCE_ESTEP_F32=0 disables)
     int tri;                   // V16 per-group bounds T_3 / T_1 (SBCE_ESTEP_TRI: 0 off, 1 built once
                                // kTriGate groups of the symbol reached the screen, 2 always built)
+    int order;                 // V16 soft sweep: best-first column tiles and row blocks (A/B build:
+                               // SBCE_ESTEP_ORDER=0 is the natural order; the product build has it on)
 };
 
 // V16 (M == 16, NA == 2): the A operand's V term, V[kk][i & 15] = V[kk][lane & 15], is the
@@ -704,23 +706,73 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     const double hard_bound = d0 + 1e-10 * cscale_d + 1e-300;
     unsigned groups = 0;             // wave-uniform count of issued tile groups
     unsigned reached = 0;            // ... and of tile groups that reached the screen
+    // Best-first order (V16, soft).  The running minimum starts at the ridge-rounded candidate,
+    // a poor hypothesis at theta_0's ill-conditioned H_eff, and every group met before the true
+    // minimum is tested against a loose skip bound.  So the 16 column tiles are visited by
+    // ascending column-tile bound and, inside one, the four row blocks by ascending minimum of
+    // their row-tile bounds: the tiles that can hold the minimum come first.  Both bounds exist
+    // before the sweep and depend on no switch, a skipped group holds nothing the posterior
+    // keeps, so the moments change in summation order alone.  Ties keep the smaller index (all
+    // bounds equal, or all below their rounding margin as at n_rx <= 2, is the natural order).
+    // The hard decision is "the first minimum in product order" and keeps the natural order.
+    // The order is wave-uniform: 16 nibbles (kt at position n) and 4 x 2 bits (block at
+    // position n), in scalar registers.
+    constexpr bool ORD = V16 && MODE != SBCE_ESTEP_HARD;
+    const bool ordered = ORD && (SBCE_AB ? c.order != 0 : true);
+    unsigned long long ktord = 0xfedcba9876543210ull;
+    if constexpr (ORD) {
+        if (ordered) {
+            // a bound below its own rounding margin says nothing (n_rx <= 2: P = 0 up to
+            // rounding): such bounds tie at 0 and keep the natural order among themselves
+            const double lbc = lbp[col];
+            const double mine = lbc < lb_margin ? 0.0 : lbc;
+            int rank = 0;            // tiles in front of tile `col`: smaller bound, or equal and smaller index
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const double lbj = lbp[j];
+                const double o = lbj < lb_margin ? 0.0 : lbj;
+                rank += (o < mine || (o == mine && j < col)) ? 1 : 0;
+            }
+            // the ranks are a permutation: tile col goes to nibble `rank`; OR over the 16 lanes
+            // of a row (every row computes the same) by DPP, as wave_min_dpp reduces
+            const unsigned nib = (unsigned)col << ((rank & 7) << 2);
+            unsigned lo = rank < 8 ? nib : 0u, hi = rank < 8 ? 0u : nib;
+            auto row_or = [](unsigned v) {
+                v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+                v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+                v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
+                v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);
+                return (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+            };
+            lo = row_or(lo);
+            hi = row_or(hi);
+            ktord = ((unsigned long long)hi << 32) | lo;
+        }
+    }
     // column tiles whose exact bound (column_tile_bounds) admits the skip bound as it stands
     // now; the bound only falls during the sweep, so each is checked again when reached
-    unsigned long long ktmask = ~0ull;
-    if (nktile <= 64) {
+    [[maybe_unused]] unsigned long long ktmask = ~0ull;
+    if (!ORD && nktile <= 64) {
         const double lim0 = ((MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d) + lb_margin;
         ktmask = __ballot(lane < nktile && !(lbp[lane < nktile ? lane : 0] > lim0));
     }
-    for (int kt = 0; kt < nktile; ++kt) {
-        if (nktile <= 64) {
+    // (kn: the position in the order, which sets kt; the natural sweep counts kt itself)
+    for (int kt = 0, kn = 0; (ORD ? kn : kt) < nktile; ++kt, ++kn) {
+        if constexpr (ORD) {
+            kt = (int)(ktord >> (4 * kn)) & 15;
+        } else if (nktile <= 64) {
             const unsigned long long m = ktmask >> kt;
             if (!m) break;
             kt += __builtin_ctzll(m);
         }
-        // exact column-tile bound: wave-uniform skip of the whole tile
-        if (lbp[kt] > ((MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d) + lb_margin)
+        // exact column-tile bound: wave-uniform skip of the whole tile (best-first: the bounds
+        // ascend and the skip bound only falls, so the first tile above it ends the symbol)
+        if (lbp[kt] > ((MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d) + lb_margin) {
+            if (ORD && ordered) break;
             continue;
+        }
         unsigned rowmask = 0xffffu;
+        [[maybe_unused]] unsigned blkord = 0xe4u;    // row blocks 0, 1, 2, 3
         if constexpr (V16) {
             // per-group bounds: built once kTriGate groups of the symbol have reached the screen
             // (the later E-steps' symbols, with a group or two left, never pay for the tables);
@@ -732,21 +784,50 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
             if (tri_have) {
                 const double lim = (MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d;
                 const unsigned long long lv = __ballot(tri_lane <= lim) >> kt;   // bit 16 blk: group alive
-                if (!(lv & 0x0001000100010001ull)) continue;
                 rowmask = ((lv & 1) ? 0x000fu : 0u) | ((lv >> 16 & 1) ? 0x00f0u : 0u) |
                           ((lv >> 32 & 1) ? 0x0f00u : 0u) | ((lv >> 48 & 1) ? 0xf000u : 0u);
             }
         }
+        unsigned rowlive = 0xffffu;                      // row tiles the row-tile bound admits
+        double bnd = INFINITY;
         if (rowb) {
-            double bnd = INFINITY;
             if (lane < 16) {
                 const cd x0 = s_cons[lane];
                 const double* rk = s_rk + 3 * kt;
                 bnd = fma(cabs2(x0), s_tab[63], rk[0] - 2.0 * (x0.x * rk[1] + x0.y * rk[2]));
             }
             const double lim = ((MODE == SBCE_ESTEP_HARD) ? hard_bound : mshift + thr_d) + lb_margin;
-            rowmask &= (unsigned)__ballot(bnd <= lim);
-            if (!rowmask) continue;                      // no row tile of this column survives
+            rowlive = (unsigned)__ballot(bnd <= lim);
+        }
+        if constexpr (V16) {
+            // A group the row bound admits and the per-group bound rejects is one the screen would
+            // have rejected: it counts in the screen's pass rate, so that the screen stops for the
+            // same symbols with and without the per-group bounds (these never add an FP64 group).
+            if (tri_have && scr_on) {
+                unsigned rl = rowlive | (rowlive >> 1);
+                rl |= rl >> 2;                           // bit 4 blk: a row tile of the block is admitted
+                scr_n += __builtin_popcount(rl & ~rowmask & 0x1111u);
+            }
+        }
+        rowmask &= rowlive;
+        if (!rowmask) continue;                          // no group of this column tile survives
+        if constexpr (ORD) {
+            if (rowb && ordered) {
+                // block minimum of the row bounds (lanes 4 blk .. 4 blk + 3), ranked as above
+                double bm = fmin(bnd, dpp_d<0xB1>(bnd));
+                bm = fmin(bm, dpp_d<0x4E>(bm));
+                bm = bm < lb_margin ? 0.0 : bm;
+                const int blk = (lane >> 2) & 3;
+                int rank = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double o = lane_d(bm, 4 * j);
+                    rank += (o < bm || (o == bm && j < blk)) ? 1 : 0;
+                }
+                const int code = blk << (2 * rank);
+                blkord = (unsigned)(__builtin_amdgcn_readlane(code, 0) | __builtin_amdgcn_readlane(code, 4) |
+                                    __builtin_amdgcn_readlane(code, 8) | __builtin_amdgcn_readlane(code, 12));
+            }
         }
         const int k = kt * 16 + col;
         cd xb[NB];
@@ -856,16 +937,18 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                 wave_sync();
                 table_ready = (k_JA == k_chunk);
             }
-            for (int tg = 0; tg < ntile_chunk; tg += TU) {
+            for (int tg = 0, tn = 0; (ORD ? tn : tg) < ntile_chunk; tg += TU, tn += TU) {
                 // TU independent 16x16 tiles in flight: STEPS*TU MFMAs per group;
                 // accumulators start at alpha_i, gamma_k (lane constant) stays outside
+                if constexpr (ORD) tg = (int)((blkord >> (tn >> 1)) & 3u) << 2;   // TU = 4: position tn / 4
                 if (V16 && !((rowmask >> tg) & ((1u << TU) - 1u))) continue;
                 if constexpr (V16) {
                     // again as the group is reached (the skip bound falls inside a column tile
                     // too; hard: the lanes' own running minima)
-                    if (tri_have && !__any(lane_d(tri_lane, kt + 4 * tg) <=
-                                           ((MODE == SBCE_ESTEP_HARD) ? best_d : mshift + thr_d)))
-                        continue;
+                    const bool dead = tri_have && !__any(lane_d(tri_lane, kt + 4 * tg) <=
+                                                         ((MODE == SBCE_ESTEP_HARD) ? best_d : mshift + thr_d));
+                    scr_n += (int)(dead & scr_on);
+                    if (dead) continue;
                 }
                 ++reached;
                 if (V16 && scr_on) {
@@ -1190,6 +1273,7 @@ bool make_mfma(const Problem& pb, MfmaConst& c, size_t& lds, long& blocks) {
     c.spw = 4;                                           // symbols per wave
     c.screen = !g_debug.estep_nof32;                     // FP32 tile-group screen (V16)
     c.tri = g_debug.estep_tri;                           // per-group bounds (V16)
+    c.order = !g_debug.estep_noorder;                    // best-first order (V16, soft)
     c.rowb = pb.NT == 4 && c.prune;
     lds = 64 * sizeof(cd) + (size_t)kMfmaWaves * c.tab_d * sizeof(double);
     const long nsym = (long)pb.B * pb.Td;

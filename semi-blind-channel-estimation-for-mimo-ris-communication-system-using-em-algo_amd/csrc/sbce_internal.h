@@ -270,9 +270,11 @@ struct DebugConfig {
     int estep_tri;       // SBCE_ESTEP_TRI=0|1|2   V16 sweep: per-group bounds T_3 / T_1 off / built once
                          //                        a symbol's groups keep reaching the screen (the
                          //                        default) / built for every swept symbol
+    bool estep_noorder;  // SBCE_ESTEP_ORDER=0     V16 soft sweep: column tiles and row blocks in natural
+                         //                        order instead of best-first (by their bounds)
 };
 inline constexpr DebugConfig kDebugDefault = {false, false, false, false, false, 128, false, false,
-                                              false, true, false, false, false, 0, false, 0, 1};
+                                              false, true, false, false, false, 0, false, 0, 1, false};
 #if SBCE_AB
 extern DebugConfig g_debug;
 #else

@@ -4,12 +4,14 @@ generator signal_model.synthetic_batch, no device and no library) of the V16 E-s
 (n_tx = 4, 16-QAM): which of the 64 tile groups G(kt, tg) -- x_2 = cons[kt], x_0 in
 cons[tg .. tg+3], every x_1 and x_3 -- survive the column-tile bound (P-perp of span(h_0, h_1)),
 the row-tile bound (P-perp of span(h_1, h_3)) and the per-group bounds T_3 / T_1 (one stream
-relaxed) and reach the FP32 screen, and which pass it to the FP64 MFMAs.  Natural sweep order,
-the running minimum starting at the ridge-rounded candidate, the device's constants (csrc/estep_sweep.hip:
+relaxed) and reach the FP32 screen, and which pass it to the FP64 MFMAs.  The device's best-first
+order (visit_order; "natural" is kept for the record), the running minimum starting at the
+ridge-rounded candidate, the device's constants (csrc/estep_sweep.hip:
 threshold 50 varn^2, ridge 0.1 varn^2, the margins of lb_margin, the screen and build_tri; the
 per-group tables rounded to float32 as the device forms them).
 
-Run as a script it rebuilds the table of profiles/tribound/README.md:
+Run as a script it rebuilds the tables of profiles/tribound/README.md (natural order) and of
+profiles/sweep_order/README.md (both orders):
   python tools/e0_group_bounds.py [snr ...]        (default 20 30 10)
 on synthetic_batch(4, 4, 4, 64, 16, 256, 16, varn, seed=2) at theta_0, symbols t = 0, 16, .., 240.
 """
@@ -89,11 +91,32 @@ def tri_bound(H, y, cons, q):
     return tmin.reshape(4, 4, 16).min(axis=1) + qq[None, :] - margin[None, :]
 
 
-def symbol(H, y, cons, varn, mode="both", gate=0, thr_scale=1.0):
-    """One symbol's sweep.  mode: 'off' (today's two bounds), 't3' (third-stream bound only) or
-    'both'; gate: groups at the screen before the tables exist (0: from the start).  Returns a
-    dict: screen / fp64 group counts, within (hypotheses inside the final threshold), skipped
-    (set of (kt, blk) the per-group bounds removed), shift (the final running minimum), d."""
+def visit_order(lb, rb, order="device", margin=0.0):
+    """The soft sweep's visiting order: the column tiles, and per column tile its four row blocks.
+    'device': column tiles by ascending column-tile bound lb[kt], the row blocks of tile kt by
+    ascending block minimum of the row-tile bound rb[s0, kt], ties to the smaller index (stable),
+    a bound below `margin` (the device's lb_margin) counting as 0;
+    'natural': 0, 1, 2, ... (the order before best-first, and the hard decision's)."""
+    if order == "natural":
+        return list(range(16)), [list(range(4))] * 16
+    if order != "device":
+        raise ValueError(order)
+    key = lambda v: np.where(v < margin, 0.0, v)         # a bound below its rounding margin ties at 0
+    kts = [int(k) for k in np.argsort(key(lb), kind="stable")]
+    blks = [[int(b) for b in np.argsort(key(rb[:, kt].reshape(4, 4).min(axis=1)), kind="stable")]
+            for kt in range(16)]
+    return kts, blks
+
+
+def symbol(H, y, cons, varn, mode="both", gate=0, thr_scale=1.0, order="device"):
+    """One symbol's soft sweep.  mode: 'off' (column- and row-tile bounds only), 't3' (third-stream
+    bound only) or 'both'; gate: groups at the screen before the tables exist (0: from the start);
+    order: visit_order's.  As on the device the column-tile bound is tested when a tile is reached
+    (in the device's order the first tile above the limit ends the symbol), the row-tile test is
+    made once on entering a column tile, and the per-group bound and the screen are tested as each
+    block is reached.  Returns a dict: screen / fp64 group counts, within (hypotheses inside the
+    final threshold), skipped (set of (kt, blk) the per-group bounds removed), swept (set of
+    (kt, blk) that ran in FP64), shift (the final running minimum), d."""
     c = np.asarray(cons)
     nr = len(y)
     d, al, ga = distances(H, y, c)
@@ -127,21 +150,28 @@ def symbol(H, y, cons, varn, mode="both", gate=0, thr_scale=1.0):
     gmin = d.reshape(4, 4, 16, 16, 16).min(axis=(1, 2))  # [blk, kt, x3]: group minima per column
     screen = fp64 = scr_n = scr_pass = 0
     scr_on, have = True, False
-    skipped = set()
-    for kt in range(16):
+    skipped, swept = set(), set()
+    kts, blks = visit_order(lb, rb, order, lbm)
+    for kt in kts:
         if lb[kt] > shift + thr + lbm:
+            if order == "device":
+                break                # the bounds ascend, the limit only falls
             continue
         if mode != "off" and not have and screen >= gate:
             have = True
-        if have and not (tri[:, kt] <= shift + thr).any():
-            skipped.update((kt, blk) for blk in range(4) if (rb[4 * blk:4 * blk + 4, kt] <= shift + thr + lbm).any())
-            continue
         rows = rb[:, kt] <= shift + thr + lbm
-        for blk in range(4):
-            if not rows[4 * blk:4 * blk + 4].any():
+        # blocks the row bound admits and the per-group bound rejects on entering the tile: they
+        # count as rejections in the screen's pass rate (so do the ones rejected when reached)
+        dead = [blk for blk in range(4) if have and rows[4 * blk:4 * blk + 4].any() and tri[blk, kt] > shift + thr]
+        skipped.update((kt, blk) for blk in dead)
+        if scr_on:
+            scr_n += len(dead)
+        for blk in blks[kt]:
+            if not rows[4 * blk:4 * blk + 4].any() or blk in dead:
                 continue
             if have and tri[blk, kt] > shift + thr:
                 skipped.add((kt, blk))
+                scr_n += scr_on
                 continue
             screen += 1
             gm = gmin[blk, kt]
@@ -154,22 +184,24 @@ def symbol(H, y, cons, varn, mode="both", gate=0, thr_scale=1.0):
                 if not ok:
                     continue
             fp64 += 1
+            swept.add((kt, blk))
             if gm.min() <= shift + thr:
                 shift = min(shift, gm.min())
     return dict(screen=screen, fp64=fp64, within=int((d <= d.min() + thr).sum()), skipped=skipped,
-                shift=shift, d=d, tri=tri)
+                swept=swept, shift=shift, d=d, tri=tri, lb=lb, rb=rb)
 
 
-def count_groups(batch, theta, varn, tri=True, gate=0, symbols=None):
+def count_groups(batch, theta, varn, tri=True, gate=0, symbols=None, order="device"):
     """Totals over the batch's symbols (or the (b, t) pairs given) of the groups that reach the
-    screen and of the FP64 groups, as the device's counters count them."""
+    screen and of the FP64 groups, as the device's counters count them (order: visit_order's)."""
     H = heff(batch, theta)
     y = np.asarray(batch["y_d"])
     if symbols is None:
         symbols = [(b, t) for b in range(H.shape[0]) for t in range(H.shape[1])]
     tot = dict(screen=0, fp64=0, within=0, symbols=len(symbols))
     for b, t in symbols:
-        r = symbol(H[b, t], y[b, t], batch["cons"], varn, "both" if tri is True else (tri or "off"), gate)
+        r = symbol(H[b, t], y[b, t], batch["cons"], varn, "both" if tri is True else (tri or "off"), gate,
+                   order=order)
         for k in ("screen", "fp64", "within"):
             tot[k] += r[k]
     return tot
@@ -186,13 +218,15 @@ def main():
         varn = float(sm.snr_to_varn(snr))
         b = sm.synthetic_batch(4, 4, 4, 64, 16, 256, 16, varn, seed=2)
         sy = [(i, t) for i in range(4) for t in range(0, 256, 16)]
-        off = count_groups(b, b["theta0"], varn, tri=False, symbols=sy)
-        both = count_groups(b, b["theta0"], varn, tri=True, symbols=sy)
-        t3 = count_groups(b, b["theta0"], varn, tri="t3", symbols=sy)
-        gated = count_groups(b, b["theta0"], varn, tri=True, gate=GATE, symbols=sy)
         n = len(sy)
-        print(f"{snr:7.0f} {off['within'] / n:11.1f} {off['screen'] / n:10.1f} {off['fp64'] / n:6.1f} "
-              f"{both['screen'] / n:7.1f} {t3['screen'] / n:8.1f} {gated['screen'] / n:7.1f}")
+        for order in ("natural", "device"):
+            off = count_groups(b, b["theta0"], varn, tri=False, symbols=sy, order=order)
+            both = count_groups(b, b["theta0"], varn, tri=True, symbols=sy, order=order)
+            t3 = count_groups(b, b["theta0"], varn, tri="t3", symbols=sy, order=order)
+            gated = count_groups(b, b["theta0"], varn, tri=True, gate=GATE, symbols=sy, order=order)
+            print(f"{snr:7.0f} {off['within'] / n:11.1f} {off['screen'] / n:10.1f} {off['fp64'] / n:6.1f} "
+                  f"{both['screen'] / n:7.1f} {t3['screen'] / n:8.1f} {gated['screen'] / n:7.1f}"
+                  f"   {order} order: FP64 groups {both['fp64'] / n:.2f} (T3+T1), {gated['fp64'] / n:.2f} (gated)")
 
 
 if __name__ == "__main__":

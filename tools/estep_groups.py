@@ -2,7 +2,9 @@
 groups that reach the FP32 screen (sbce_debug_estep_groups) and FP64 groups (FP64 MFMAs / 8), at
 theta_0 (the iteration-0 E-step) and after a 20-iteration EM, under alternating settings, with
 the E-step's time by HIP events (median of REPS), e.g.
-  python tools/estep_groups.py SBCE_ESTEP_TRI=0 SBCE_ESTEP_TRI=1 SBCE_ESTEP_TRI=2"""
+  python tools/estep_groups.py SBCE_ESTEP_TRI=0 SBCE_ESTEP_TRI=1 SBCE_ESTEP_TRI=2
+  python tools/estep_groups.py SBCE_ESTEP_ORDER=1 SBCE_ESTEP_ORDER=0        (best-first / natural order)
+One K=V per arm; a second switch of a combined arm is set in the environment of the run."""
 import ctypes
 import os
 import sys
