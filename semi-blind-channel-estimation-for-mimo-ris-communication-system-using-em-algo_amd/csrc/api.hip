@@ -48,6 +48,7 @@ void read_debug_env(DebugConfig& c) {
     if ((v = env("SBCE_SMALL_SOLVE"))) c.small_col = v[0] == 'c';
     if ((v = env("SBCE_ESTEP_TRI"))) c.estep_tri = (v[0] >= '0' && v[0] <= '2') ? v[0] - '0' : 1;
     if ((v = env("SBCE_ESTEP_ORDER"))) c.estep_noorder = v[0] == '0';
+    if ((v = env("SBCE_ESTEP_TWOPASS"))) c.estep_notwopass = v[0] == '0';
     if ((v = env("SBCE_SMALL_STOP"))) c.small_stop = (v[0] >= '1' && v[0] <= '4') ? v[0] - '0' : 0;
 }
 
@@ -59,6 +60,7 @@ bool debug_nondefault() {
     const DebugConfig& d = kDebugDefault;
     return c.estep_valu != d.estep_valu || c.estep_noprune != d.estep_noprune ||
            c.estep_nof32 != d.estep_nof32 || c.estep_tri != d.estep_tri || c.estep_noorder != d.estep_noorder ||
+           c.estep_notwopass != d.estep_notwopass ||
            c.estep_nosphere != d.estep_nosphere || c.sphere_budget != d.sphere_budget ||
            c.backsub_general != d.backsub_general || c.chol_valu != d.chol_valu ||
            c.estep_nopair != d.estep_nopair || c.cplx3 != d.cplx3 ||
@@ -1021,6 +1023,14 @@ int sbce_debug_estep_mfma(unsigned long long* out, int reset) {
 int sbce_debug_estep_groups(unsigned long long* out, int reset) {
     if (!reset && !out) return SBCE_EINVAL;
     return hip_rc(estep_debug_groups(out, reset));
+}
+
+// Diagnostic, not part of include/sbce.h: tile groups the second pass of the two-pass V16 soft
+// sweep recomputed since the last reset (counted only with SBCE_ESTEP_COUNT=1; 8 FP64 MFMAs each,
+// on top of sbce_debug_estep_mfma, which stays the search's count); reset != 0 clears the counter.
+int sbce_debug_estep_pass2(unsigned long long* out, int reset) {
+    if (!reset && !out) return SBCE_EINVAL;
+    return hip_rc(estep_debug_pass2(out, reset));
 }
 
 // Diagnostic, not part of include/sbce.h: trial-M-steps the moment-repeat rule of sbce_em skipped

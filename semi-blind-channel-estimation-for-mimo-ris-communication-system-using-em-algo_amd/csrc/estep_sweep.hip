@@ -134,6 +134,8 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // 2 x staged record (DMA double buffer: 128 + 32 done words, or the record itself) |
 // FP32 screen tables (V16: alpha and U as floats, kScreenD doubles)
 constexpr int mfma_rec_d(int rec_words) { return 2 * (rec_words <= 128 ? 160 : (rec_words + 1) / 2 * 2 + 32); }
+// one half of that double buffer in the V16 layout (record 4 + 2 NT NR + 16 + 6 NR, y_t 2 NR)
+constexpr int mfma_rec_half_v16(int NT, int NR) { return mfma_rec_d(4 + 2 * NT * NR + 16 + 8 * NR) / 2; }
 // ... | per-group bound tables (V16, i.e. M = 16 with a 256-row chunk: U', V', Q' as floats,
 // 64 steps each, then 256 floats that hold the projected vectors and after them alpha')
 constexpr int mfma_tri_d(int steps) { return 3 * 64 * steps / 2 + 128; }
@@ -160,6 +162,8 @@ struct MfmaConst {
     int screen;                // V16 FP32 screen of the tile groups (SBCE_ESTEP_F32=0 disables)
     int tri;                   // V16 per-group bounds T_3 / T_1 (SBCE_ESTEP_TRI: 0 off, 1 built once
                                // kTriGate groups of the symbol reached the screen, 2 always built)
+    int twopass;               // V16 soft sweep: search, then accumulate (A/B build: SBCE_ESTEP_TWOPASS=0
+                               // is the one-pass sweep; the product build has the two-pass one alone)
     int order;                 // V16 soft sweep: best-first column tiles and row blocks (A/B build:
                                // SBCE_ESTEP_ORDER=0 is the natural order; the product build has it on)
 };
@@ -266,10 +270,15 @@ __device__ unsigned long long g_estep_mfma;
 // ... and the V16 tile groups that survived every bound and reached the FP32 screen (the FP64
 // test with the screen off): what the bounds leave the screen to reject.
 __device__ unsigned long long g_estep_groups;
+// ... and the tile groups the two-pass sweep's second pass recomputed (8 more FP64 MFMAs each,
+// not in g_estep_mfma, which stays the search's count).
+__device__ unsigned long long g_estep_pass2;
 
-template <int NT, int NR, int MODE, int TU, bool V16>
+template <int NT, int NR, int MODE, int TU, bool V16, bool TP = false, bool REC = false>
 __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaConst& c) {
     static_assert(!V16 || NT == 4, "the V16 body is the n_tx = 4, M = 16 sweep");
+    // TP: the two-pass soft sweep (search, then accumulate; see the second pass below)
+    static_assert(!TP || (V16 && MODE == SBCE_ESTEP_SOFT && TU == 4), "two-pass: the V16 soft sweep");
     // V16 (n_tx = 4, M = 16): the layout constants are compile-time (LDS offsets fold into
     // immediates, one SGPR wave base); otherwise they come from MfmaConst
     const int k_M = V16 ? 16 : c.M;
@@ -281,7 +290,11 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     const int k_rowb_off = V16 ? 4 + 2 * NT * NR + 16 : c.rowb_off;
     const int k_prep_stride = V16 ? k_rowb_off + 6 * NR : c.prep_stride;
     const int k_rec_words = V16 ? k_prep_stride + 2 * NR : c.rec_words;
-    const int k_tab_d = V16 ? mfma_tab_d(NT * NR, 256, (2 * NR + 3) / 4, 16, 16, k_rec_words) : c.tab_d;
+    // TP: the second half of the record double buffer lies behind both waves' tables, and only
+    // in a launch without a work list (a listed grab holds one symbol and prefetches none)
+    constexpr int REC_H = mfma_rec_half_v16(NT, NR);
+    const int k_tab_d = V16 ? mfma_tab_d(NT * NR, 256, (2 * NR + 3) / 4, 16, 16, k_rec_words) - (TP ? REC_H : 0)
+                            : c.tab_d;
     constexpr int NA = NT / 2;
     constexpr int NB = NT - NA;
     constexpr int NO = NT * NR;
@@ -309,7 +322,13 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     double* s_recb = s_tab + 128;                  // 2 x [prep record | y_t (128) | done (32)]
     // V16 FP32 screen: alpha (row order: the f32 MFMA's C/D row of value q is 4 (lane >> 4) + q,
     // not the f64 form's (lane >> 4) + 4 q) and U (s_U's layout) as floats
-    float* s_al32 = reinterpret_cast<float*>(s_recb + mfma_rec_d(k_rec_words));
+    float* s_al32 = reinterpret_cast<float*>(s_recb + (TP ? REC_H : mfma_rec_d(k_rec_words)));
+    [[maybe_unused]] double* s_rec2 =
+        reinterpret_cast<double*>(s_cons + 64) + (size_t)kMfmaWaves * k_tab_d + (size_t)wave * REC_H;
+    auto rec_half = [&](int h) -> double* {
+        if constexpr (TP) return h ? s_rec2 : s_recb;
+        else return s_recb + h * 160;
+    };
     float* s_U32 = s_al32 + 256;
 
     for (int i = threadIdx.x; i < k_M; i += blockDim.x) s_cons[i] = a.cons[i];
@@ -322,7 +341,9 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     const bool listed = a.list != nullptr;
     int32_t* cnt = listed ? a.list + nsym : nullptr;
     const long nwork = listed ? (long)__builtin_amdgcn_readfirstlane(cnt[0]) : nsym;
-    const bool prep = a.prep != nullptr;
+    // REC: a launch with a prep record, known at compile time (the in-kernel preparation of the
+    // other launches, candidate_distance and column_tile_bounds, is what needs the most registers)
+    const bool prep = REC || a.prep != nullptr;
     auto sym_of = [&](long gi) -> long { return listed ? (long)a.list[gi] : gi; };
     // listed: a wave's first entry is its global wave index (no atomic -- with a short or empty
     // list most waves exit at once; 4096 same-address atomics of an empty list cost ~50 us),
@@ -371,13 +392,13 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     for (long gi = g0; gi < g1; ++gi) {
     const long gsym = sym_of(gi);
     const int cur = (int)((gi - g0) & 1);
-    double* s_rec = s_recb + cur * 160;
+    double* s_rec = rec_half(cur);
     int dn;
     if (dma) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this symbol's record has landed
         wave_sync();
         dn = a.done ? reinterpret_cast<const int*>(s_rec + 128)[0] : 0;
-        if (gi + 1 < g1) issue(sym_of(gi + 1), s_recb + (cur ^ 1) * 160);
+        if (gi + 1 < g1) issue(sym_of(gi + 1), rec_half(cur ^ 1));
     } else {
         dn = a.done ? a.done[gsym / c.Td] : 0;
         if (prep && !dn) {
@@ -705,6 +726,8 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
 
     const double hard_bound = d0 + 1e-10 * cscale_d + 1e-300;
     unsigned groups = 0;             // wave-uniform count of issued tile groups
+    // TP: bit 4 kt + row block of every group that passed the search's FP64 test (wave-uniform)
+    [[maybe_unused]] unsigned long long hit = 0;
     unsigned reached = 0;            // ... and of tile groups that reached the screen
     // Best-first order (V16, soft).  The running minimum starts at the ridge-rounded candidate,
     // a poor hypothesis at theta_0's ill-conditioned H_eff, and every group met before the true
@@ -1014,6 +1037,14 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                 } else if (!__any(cm + gam <= mshift + thr_d)) {
                     continue;
                 }
+                if constexpr (TP) {
+                    // the search keeps the running minimum (the same sequence of values as the
+                    // one-pass sweep, so every skip decision is that sweep's) and marks the group
+                    cm += gam;
+                    if (__any(cm < mshift)) mshift = wave_min_dpp(fmin(cm, mshift));
+                    hit |= 1ull << (4 * kt + (tg >> 2));
+                    continue;
+                }
                 if (MODE == SBCE_ESTEP_HARD) {
                     const double lim = best_d - gam;
 #pragma unroll
@@ -1095,7 +1126,7 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
                 }
             }
         }
-        if (MODE == SBCE_ESTEP_SOFT && touched) {
+        if (!TP && MODE == SBCE_ESTEP_SOFT && touched) {
             if constexpr (V16) {
                 // the lane's row streams x_s1 = cons[rq + 4 j]
                 ck = (R1[0] + R1[1]) + (R1[2] + R1[3]);
@@ -1126,6 +1157,86 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
             }
         }
     }
+    // Second pass (TP).  The search above held no posterior sum: the 25 lane totals and the
+    // per-column-tile R1 / Q / N0 are live only from here on, which is what lets the search run at
+    // three waves per SIMD.  The minimum d_min = mshift is final, so the weights are
+    // exp((d_min - d) / s^2) directly and nothing is ever rescaled.  The marked groups are visited
+    // in natural order (kt ascending, row block ascending), whatever order the search took; each
+    // is recomputed tile by tile with the same FP64 MFMAs on the same operands (bitwise the
+    // search's distances), and a tile that holds nothing within d_min + thr_d (its group was
+    // marked under an earlier, looser minimum, or by another tile) is dropped.  The sums are the
+    // one-pass sweep's factored ones.
+    [[maybe_unused]] unsigned groups2 = 0;           // wave-uniform count of recomputed groups
+    if constexpr (TP) {
+        for (unsigned long long left = hit; left;) {
+            const int kt = __builtin_ctzll(left) >> 2;
+            const unsigned blks = (unsigned)(left >> (4 * kt)) & 15u;
+            left &= ~(15ull << (4 * kt));
+            double bop[STEPS];
+            double gam = 0.0;
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) {
+                bop[s] = s_Q2[(4 * s + rq) * 16 + kt] + q3reg[s];
+                gam = fma(bop[s], bop[s], gam);
+            }
+            gam += bperm_d(gam, xaddr16);
+            gam += bperm_d(gam, xaddr32);
+            double R1[4] = {0.0, 0.0, 0.0, 0.0}, N0 = 0.0;
+            cd Q[4] = {czero(), czero(), czero(), czero()};
+            bool touched = false;
+            groups2 += __builtin_popcount(blks);
+            // one tile at a time (marked groups are few; the search's registers set the allocation)
+#pragma unroll 1
+            for (int tl = 0; tl < 16; ++tl) {
+                if (!((blks >> (tl >> 2)) & 1u)) continue;
+                const cd lo = *reinterpret_cast<const cd*>(s_al + tl * 16 + rq * 4);
+                const cd hi = *reinterpret_cast<const cd*>(s_al + tl * 16 + rq * 4 + 2);
+                mf4 acc = mf4{lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s)
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(s_U[(4 * s + rq) * 16 + tl] + vreg[s], bop[s],
+                                                               acc, 0, 0, 0);
+                const double cmu = fmin(fmin(acc[0], acc[1]), fmin(acc[2], acc[3])) + gam;
+                if (!__any(cmu <= mshift + thr_d)) continue;
+                touched = true;
+                const cd x0 = s_cons[tl];                      // stream 0 of the tile
+                const double n0 = cabs2(x0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double dj = acc[j] + gam;
+                    // rows with no lane inside the bound: weights < e^-50 of the maximum
+                    if (!__any(dj <= mshift + thr_d)) continue;
+                    const double w = fexp_neg((mshift - dj) * inv_s2);
+                    R1[j] += w;
+                    Q[j] = caxpy(Q[j], w, x0);
+                    N0 = fma(w, n0, N0);
+                }
+            }
+            if (!touched) continue;
+            // the column tile's sums into the totals, as the one-pass sweep folds them
+            const cd x2 = s_cons[kt];                          // stream 2 of the column tile
+            const double ck = (R1[0] + R1[1]) + (R1[2] + R1[3]);
+            cd mu[NA];
+            mu[0] = cadd(cadd(Q[0], Q[1]), cadd(Q[2], Q[3]));
+            mu[1] = czero();
+            nu[0] += N0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const cd x1 = s_cons[rq + 4 * j];
+                mu[1] = caxpy(mu[1], R1[j], x1);
+                nu[1] = fma(R1[j], cabs2(x1), nu[1]);
+                kap = cadd(kap, cmulc(Q[j], x1));
+            }
+            tot_c += ck;
+            tot_mB[0] = caxpy(tot_mB[0], ck, x2);
+            tot_nB[0] = fma(ck, cabs2(x2), tot_nB[0]);
+#pragma unroll
+            for (int q = 0; q < NA; ++q) {
+                tot_muA[q] = cadd(tot_muA[q], mu[q]);
+                tot_X[q][0] = cfmac(tot_X[q][0], mu[q], x2);
+            }
+        }
+    }
     if constexpr (V16) {
         // stream 3 is the lane constant x_3 = cons[col] (k = 16 kt + col): its sums are the
         // lane's totals times x_3
@@ -1140,6 +1251,7 @@ __device__ __forceinline__ void estep_mfma_body(const EstepArgs& a, const MfmaCo
     if (c.count && lane == 0) {
         atomicAdd(&g_estep_mfma, (unsigned long long)groups * STEPS * TU);
         if (V16) atomicAdd(&g_estep_groups, (unsigned long long)reached);
+        if (TP) atomicAdd(&g_estep_pass2, (unsigned long long)groups2);
     }
     constexpr int MS = NT + NT * NT;
     cd* out = a.mom + (size_t)gsym * MS;
@@ -1247,6 +1359,11 @@ template <int NT, int NR, int MODE, int TU, bool V16 = false>
 __global__ __launch_bounds__(128) void estep_mfma_kernel(EstepArgs a, MfmaConst c) {
     estep_mfma_body<NT, NR, MODE, TU, V16>(a, c);
 }
+// The two-pass V16 soft sweep.  WPE: the waves per SIMD the register allocation is asked to reach.
+template <int NR, bool REC>
+__global__ __launch_bounds__(128) void estep_twopass_kernel(EstepArgs a, MfmaConst c) {
+    estep_mfma_body<4, NR, SBCE_ESTEP_SOFT, 4, true, true, REC>(a, c);
+}
 bool make_mfma(const Problem& pb, MfmaConst& c, size_t& lds, long& blocks) {
     HypSplit h;
     if (!hyp_split(pb, h) || h.JA < 16 || h.JB < 16) return false;    // (n_tx = 1: JA = 1)
@@ -1274,6 +1391,7 @@ bool make_mfma(const Problem& pb, MfmaConst& c, size_t& lds, long& blocks) {
     c.screen = !g_debug.estep_nof32;                     // FP32 tile-group screen (V16)
     c.tri = g_debug.estep_tri;                           // per-group bounds (V16)
     c.order = !g_debug.estep_noorder;                    // best-first order (V16, soft)
+    c.twopass = !g_debug.estep_notwopass;                // two-pass V16 soft sweep
     c.rowb = pb.NT == 4 && c.prune;
     lds = 64 * sizeof(cd) + (size_t)kMfmaWaves * c.tab_d * sizeof(double);
     const long nsym = (long)pb.B * pb.Td;
@@ -1292,12 +1410,26 @@ hipError_t dispatch_mfma_mode(const MfmaConst& c, size_t lds, long blocks, const
             if (c.JA != 256 || c.JB != 256 || c.chunk != 256 || c.nkt_pad != 16 ||
                 c.prep_stride != 4 + 2 * NT * NR + 16 + 6 * NR)
                 return hipErrorInvalidValue;
-            if (mode == SBCE_ESTEP_HARD)
+            if (mode == SBCE_ESTEP_HARD) {
                 hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_HARD, 4, true>),
                                    dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
+                return hipGetLastError();
+            }
+            if constexpr (SBCE_AB) {              // the product build has no one-pass soft instance
+                if (!c.twopass) {
+                    hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_SOFT, 4, true>),
+                                       dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
+                    return hipGetLastError();
+                }
+            }
+            // two-pass: the record's second half only where a wave sweeps symbols in series
+            const size_t lds2 = a.list ? lds - kMfmaWaves * mfma_rec_half_v16(NT, NR) * sizeof(double) : lds;
+            if (a.prep)
+                hipLaunchKernelGGL((estep_twopass_kernel<NR, true>), dim3((unsigned)blocks),
+                                   dim3(64 * kMfmaWaves), lds2, s, a, c);
             else
-                hipLaunchKernelGGL((estep_mfma_kernel<NT, NR, SBCE_ESTEP_SOFT, 4, true>),
-                                   dim3((unsigned)blocks), dim3(64 * kMfmaWaves), lds, s, a, c);
+                hipLaunchKernelGGL((estep_twopass_kernel<NR, false>), dim3((unsigned)blocks),
+                                   dim3(64 * kMfmaWaves), lds2, s, a, c);
             return hipGetLastError();
         }
     }
@@ -1343,6 +1475,15 @@ hipError_t estep_debug_mfma(unsigned long long* out, int reset) {
         return hipMemcpyToSymbol(HIP_SYMBOL(g_estep_mfma), &z, sizeof(z), 0, hipMemcpyHostToDevice);
     }
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_estep_mfma), sizeof(*out), 0,
+                               hipMemcpyDeviceToHost);
+}
+
+hipError_t estep_debug_pass2(unsigned long long* out, int reset) {
+    if (reset) {
+        const unsigned long long z = 0;
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_estep_pass2), &z, sizeof(z), 0, hipMemcpyHostToDevice);
+    }
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_estep_pass2), sizeof(*out), 0,
                                hipMemcpyDeviceToHost);
 }
 

@@ -272,9 +272,11 @@ struct DebugConfig {
                          //                        default) / built for every swept symbol
     bool estep_noorder;  // SBCE_ESTEP_ORDER=0     V16 soft sweep: column tiles and row blocks in natural
                          //                        order instead of best-first (by their bounds)
+    bool estep_notwopass;// SBCE_ESTEP_TWOPASS=0   V16 soft sweep: the one-pass sweep (online shift, sums held
+                         //                        across the search) instead of search-then-accumulate
 };
 inline constexpr DebugConfig kDebugDefault = {false, false, false, false, false, 128, false, false,
-                                              false, true, false, false, false, 0, false, 0, 1, false};
+                                              false, true, false, false, false, 0, false, 0, 1, false, false};
 #if SBCE_AB
 extern DebugConfig g_debug;
 #else
@@ -624,6 +626,7 @@ hipError_t launch_ser(const Problem& pb, const cd* xdest, const cd* xtrue, doubl
                       hipStream_t s);
 hipError_t estep_debug_mfma(unsigned long long* out, int reset);   // SBCE_ESTEP_COUNT=1
 hipError_t estep_debug_groups(unsigned long long* out, int reset); // SBCE_ESTEP_COUNT=1
+hipError_t estep_debug_pass2(unsigned long long* out, int reset);  // SBCE_ESTEP_COUNT=1
 // every kernel launch_estep launches for (pb, mode) that writes moments folds EstepArgs::mchg
 bool estep_momfold_supported(const Problem& pb, int mode);
 // A/B build: trial-M-steps the moment-repeat rule skipped since the last reset (chol.hip)

@@ -4,6 +4,8 @@ theta_0 (the iteration-0 E-step) and after a 20-iteration EM, under alternating 
 the E-step's time by HIP events (median of REPS), e.g.
   python tools/estep_groups.py SBCE_ESTEP_TRI=0 SBCE_ESTEP_TRI=1 SBCE_ESTEP_TRI=2
   python tools/estep_groups.py SBCE_ESTEP_ORDER=1 SBCE_ESTEP_ORDER=0        (best-first / natural order)
+  python tools/estep_groups.py SBCE_ESTEP_TWOPASS=1 SBCE_ESTEP_TWOPASS=0    (two-pass / one-pass sweep)
+"second pass" is the tile groups the two-pass sweep's second pass recomputed (sbce_debug_estep_pass2).
 One K=V per arm; a second switch of a combined arm is set in the environment of the run."""
 import ctypes
 import os
@@ -35,6 +37,10 @@ def measure(arm):
     have_groups = hasattr(lib, "sbce_debug_estep_groups")     # absent before the per-group bounds
     if have_groups:
         lib.sbce_debug_estep_groups(None, 1)
+    have_pass2 = hasattr(lib, "sbce_debug_estep_pass2")       # absent before the two-pass sweep
+    p2 = ctypes.c_ulonglong(0)
+    if have_pass2:
+        lib.sbce_debug_estep_pass2(None, 1)
     lib.sbce_debug_estep_mfma(None, 1)
     lib.sbce_debug_estep_sphere(None, 1)
     lib.sbce_debug_estep_pair(None, 1)
@@ -44,6 +50,8 @@ def measure(arm):
     if have_groups:
         lib.sbce_debug_estep_groups(ctypes.byref(grp), 0)
     lib.sbce_debug_estep_mfma(ctypes.byref(mf), 0)
+    if have_pass2:
+        lib.sbce_debug_estep_pass2(ctypes.byref(p2), 0)
     lib.sbce_debug_estep_sphere(sph, 0)
     lib.sbce_debug_estep_pair(ctypes.byref(npair), 0)
     del os.environ["SBCE_ESTEP_COUNT"]
@@ -59,7 +67,7 @@ def measure(arm):
     del os.environ[k]
     pkg._lib.reload_debug_env()
     swept = int(sph[1]) - npair.value if os.environ.get("SBCE_ESTEP_SPHERE") != "0" else nsym
-    return swept, grp.value, mf.value // 8, float(np.median(ms))
+    return swept, grp.value, mf.value // 8, p2.value, float(np.median(ms))
 
 
 for label, its in (("theta_0", 0), ("after 20 EM its", 20)):
@@ -67,7 +75,8 @@ for label, its in (("theta_0", 0), ("after 20 EM its", 20)):
         eng.run(its)
         torch.cuda.synchronize()
     for arm in sys.argv[1:] or ["SBCE_ESTEP_TRI=1"]:
-        swept, grp, g64, ms = measure(arm)
+        swept, grp, g64, g2, ms = measure(arm)
         n = max(swept, 1)
         print(f"{label:16s} {arm:18s} listed {swept:6d} of {nsym}  to screen {grp / n:6.2f}  "
-              f"FP64 groups {g64 / n:6.2f} per listed symbol   E-step {ms:7.3f} ms", flush=True)
+              f"FP64 groups {g64 / n:6.2f}  second pass {g2 / n:5.2f} per listed symbol   "
+              f"E-step {ms:7.3f} ms", flush=True)
