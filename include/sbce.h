@@ -645,6 +645,54 @@ int sbce_detect_linear_workspace_bytes(const sbce_linear_dims* d, size_t* bytes)
  * SBCE_EUNSUPPORTED: n_tx > 8 or n_rx > 8; SBCE_EWORKSPACE. */
 int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, void* hip_stream);
 
+/* ---- Cramer-Rao bounds and the predicted NMSE (an additive extension of ABI 7: no existing
+ * struct or entry point changes).  In the reduced form y = H_c u + n, u = psi (x) x,
+ * n ~ CN(0, sigma^2 I), the normal matrix of the M-step is
+ *   R = sum_p u_p u_p^H + sum_t (psi_t psi_t^H) (x) S_t          (L x L, L = n_psi n_tx).
+ * With the regressors known every row of the least-squares estimate has covariance sigma^2 R^-1,
+ * so E||theta_hat - theta||^2 = n_rx sigma^2 tr(R^-1) -- also the Cramer-Rao bound -- and the
+ * variance of coefficient (l, r) is sigma^2 (R^-1)_ll.  The moments given to the build select the
+ * quantity: zero moments (S_t = 0) give the pilot-only bound; m_t = x_t, S_t = x_t x_t^H the bound
+ * with all data known (the floor of every semi-blind curve); an E-step's moments the
+ * complete-data error variance of the estimate made from them, which ignores the information lost
+ * to symbol uncertainty and so is optimistic.
+ * Per trial: R = G G^H, W = G^-1, diag_inv[l] = sum_{k >= l} |W_kl|^2, tr_inv = sum_l diag_inv[l].
+ * Pivot rule (SBCE_SOLVE_CHOL's threshold): a Cholesky pivot that is not above 1e-14 max_l R_ll --
+ * a NaN pivot included -- makes the trial unidentifiable: tr_inv, mse, bound and every diag_inv
+ * entry of the trial are +inf and it gets SBCE_STATUS_NONHPD; other trials are unaffected.
+ * Nothing is dropped or regularised: a bound on a subspace is not the bound. */
+typedef struct sbce_crb_opts {
+    double sigma2;           /* > 0: the noise variance the data carry (varn of the signal model,
+                                NOT the posterior's varn^2) */
+    const double* sigma2_t;  /* may be NULL: [B] per-trial values > 0, used instead of sigma2 */
+    double* tr_inv;          /* [B] out: tr(R^-1) */
+    double* diag_inv;        /* may be NULL: [B][L] out, (R^-1)_ll */
+    double* mse;             /* may be NULL: [B] out, n_rx sigma_b^2 tr(R^-1) */
+    double* bound;           /* may be NULL (requires p->h_true): [B] out, mse / ||h_true_b||^2 */
+    void* scratch;           /* device scratch, 16-byte aligned */
+    size_t scratch_bytes;    /* at least sbce_crb_workspace_bytes */
+    int32_t flags;           /* 0 */
+} sbce_crb_opts;
+
+/* Device scratch of sbce_crb for `d` (the inverses of the factor's diagonal tiles, and the
+ * discarded solution of the build launch at small L).  SBCE_EUNSUPPORTED as sbce_crb. */
+int sbce_crb_workspace_bytes(const sbce_dims* d, size_t* bytes);
+
+/* R is built from p->y_p, u_p, psi_d and `moments` (sbce_estep's layout; required) by the launches
+ * of sbce_mstep's build into p->workspace (sized as for sbce_mstep with SBCE_SOLVE_CHOL), then one
+ * kernel factors and inverts it in place: the call sees the R sbce_mstep reports in r_out, lower
+ * triangle only.  p->theta, y_d, y_p and `moments` are never written; p->status, when set, is
+ * written (0, SBCE_STATUS_PILOT from the build, SBCE_STATUS_NONHPD).  d, p and `moments` are checked
+ * as sbce_mstep checks them.  No allocation, no synchronisation, no floating-point atomic; every
+ * order of summation is fixed by (L, n_rx) alone, so trial b of a B-trial call is bitwise the
+ * B = 1 call, whatever the workspace held; capturable in a HIP graph as a linear chain.
+ * Decided before any HIP call, beside sbce_mstep's own -- SBCE_EINVAL: null o, tr_inv or scratch,
+ * a misaligned pointer (8 bytes float64, 16 bytes scratch), sigma2 <= 0, bound without p->h_true,
+ * flags != 0; SBCE_EUNSUPPORTED: L = n_psi n_tx > 512 (the tiled large-L factorisation has no
+ * inverse yet); SBCE_EWORKSPACE: scratch_bytes too small. */
+int sbce_crb(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
+             const sbce_crb_opts* o, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,7 +56,8 @@ EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_noise_workspace_bytes", "sbce_noise_var", "sbce_em_noise",
             "sbce_loglik_workspace_bytes", "sbce_loglik", "sbce_conv_workspace_bytes",
             "sbce_em_conv",
-            "sbce_detect_linear_workspace_bytes", "sbce_detect_linear")
+            "sbce_detect_linear_workspace_bytes", "sbce_detect_linear",
+            "sbce_crb_workspace_bytes", "sbce_crb")
 
 
 class SbceUnavailable(RuntimeError):
@@ -145,6 +146,15 @@ class ConvOpts(ctypes.Structure):
                 ("min_iters", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("dtheta_hist", ctypes.c_void_p), ("ll_hist", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
+class CrbOpts(ctypes.Structure):
+    """sbce_crb_opts (include/sbce.h): Cramer-Rao bounds from diag(R^-1), sbce_crb."""
+    _fields_ = [("sigma2", ctypes.c_double), ("sigma2_t", ctypes.c_void_p),
+                ("tr_inv", ctypes.c_void_p), ("diag_inv", ctypes.c_void_p),
+                ("mse", ctypes.c_void_p), ("bound", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+                ("flags", ctypes.c_int32)]
 
 
 _lib = None
@@ -242,6 +252,11 @@ def load(path=None):
     lib.sbce_em_conv.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
                                  ctypes.c_int, ctypes.c_int, ctypes.POINTER(NoiseOpts),
                                  ctypes.POINTER(ConvOpts), ctypes.c_void_p]
+    lib.sbce_crb_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_crb_workspace_bytes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_crb.restype = ctypes.c_int
+    lib.sbce_crb.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_void_p,
+                             ctypes.POINTER(CrbOpts), ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

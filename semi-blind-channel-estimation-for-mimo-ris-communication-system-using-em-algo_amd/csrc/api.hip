@@ -299,6 +299,12 @@ int noise_update(const Problem& pb, const sbce_ptrs* p, const cd* mom, const int
     return hip_rc(launch_noise_final(pb, f, s));
 }
 
+// sbce_crb's scratch: the diagonal tiles' inverses, then the theta the small-L build launch solves
+// for (discarded)
+size_t crb_scratch_bytes(const Problem& pb) {
+    return align_up(crb_dinv_bytes(pb)) + align_up((size_t)pb.B * pb.K * sizeof(cd));
+}
+
 // the log-likelihood's scratch: per-symbol terms (used when the caller takes no ll_sym), then the
 // pilot block sums
 size_t loglik_sym_bytes(const Problem& pb) {
@@ -902,6 +908,49 @@ int sbce_mstep(const sbce_dims* d, const sbce_ptrs* p, const void* moments, int 
                        hipMemcpyDeviceToDevice, s) != hipSuccess)
         return SBCE_EHIP;
     return small ? SBCE_OK : hip_rc(launch_chol_solve(pb, ma, s));
+}
+
+int sbce_crb_workspace_bytes(const sbce_dims* d, size_t* bytes) {
+    Problem pb;
+    if (!bytes || !make_problem(d, pb)) return SBCE_EINVAL;
+    if (!chol_supported(pb) || pb.L > kLargeL) return SBCE_EUNSUPPORTED;
+    *bytes = crb_scratch_bytes(pb);
+    return SBCE_OK;
+}
+
+int sbce_crb(const sbce_dims* d, const sbce_ptrs* p, const void* moments, const sbce_crb_opts* o,
+             void* hip_stream) {
+    Problem pb;
+    if (!make_problem(d, pb)) return SBCE_EINVAL;
+    if (!chol_supported(pb) || pb.L > kLargeL) return SBCE_EUNSUPPORTED;
+    int rc = check_ptrs(p, pb, true, SBCE_SOLVE_CHOL);
+    if (rc) return rc;
+    if (!moments) return SBCE_EINVAL;
+    if (!o || !o->tr_inv || !o->scratch || !aligned16(o->scratch)) return SBCE_EINVAL;
+    if (((uintptr_t)o->tr_inv | (uintptr_t)o->diag_inv | (uintptr_t)o->mse | (uintptr_t)o->bound |
+         (uintptr_t)o->sigma2_t) & 7)
+        return SBCE_EINVAL;
+    if (!(o->sigma2 > 0.0) || o->flags != 0) return SBCE_EINVAL;
+    if (o->bound && (!p->h_true || !aligned16(p->h_true))) return SBCE_EINVAL;
+    if (o->scratch_bytes < crb_scratch_bytes(pb)) return SBCE_EWORKSPACE;
+    if (pb.B == 0) return SBCE_OK;
+    clear_stale_error();
+    hipStream_t s = (hipStream_t)hip_stream;
+    const Carve c = carve(pb, SBCE_SOLVE_CHOL);
+    char* ws = (char*)p->workspace;
+    if ((rc = status_init(p->status, pb.B, s))) return rc;
+    // the build of sbce_mstep; at small L it comes with the solve, whose theta goes to the scratch
+    // and whose own pivot flag is not taken (the factorisation below decides)
+    MstepArgs ma = mstep_args(pb, p, moments, ws, c, SBCE_SOLVE_CHOL);
+    char* sc = (char*)o->scratch;
+    if (mstep_small_supported(pb, SBCE_SOLVE_CHOL)) {
+        ma.theta = (cd*)(sc + align_up(crb_dinv_bytes(pb)));
+        ma.status = nullptr;
+        if ((rc = hip_rc(launch_mstep_small(pb, ma, true, s)))) return rc;
+    } else if ((rc = hip_rc(launch_mstep_build(pb, ma, s)))) {
+        return rc;
+    }
+    return hip_rc(launch_crb(pb, ma.R, (cd*)sc, (const cd*)p->h_true, *o, p->status, s));
 }
 
 // Diagnostic, not part of include/sbce.h: HIP-event timing of the L <= 512 Cholesky's update /

@@ -792,4 +792,10 @@ struct ConvArgs {
 hipError_t launch_conv_init(const Problem& pb, const cd* theta, cd* prev, hipStream_t s);
 hipError_t launch_conv_step(const Problem& pb, ConvArgs c, hipStream_t s);
 
+// Cramer-Rao bound (crb.hip, sbce_crb): one launch after the M-step's build; L <= kLargeL.
+// R [B][L][L]: the build's lower triangle, overwritten; dinv: crb_dinv_bytes of scratch
+size_t crb_dinv_bytes(const Problem& pb);
+hipError_t launch_crb(const Problem& pb, cd* R, cd* dinv, const cd* h_true, const sbce_crb_opts& o,
+                      int32_t* status, hipStream_t s);
+
 }  // namespace sbce

@@ -1132,6 +1132,110 @@ def nmse_batch(theta, h):
     return out
 
 
+# ------------------------------------------------------------------ Cramer-Rao bounds
+_WANT_CRB = ("tr_inv", "mse", "diag_inv")
+
+
+def genie_moments(x_d):
+    """Moments of known data symbols x_d (..., n_tx): m = x, S = x x^H -- the E-step's output when
+    every posterior is a point mass, and the input of the all-data-known bound (crb_batch)."""
+    x = np.asarray(x_d, dtype=complex)
+    return x, x[..., :, None] * np.conj(x[..., None, :])
+
+
+def _crb_call(torch, lib, dims, ptrs, mom, sigma2, sigma2_t, have_h, want, scratch_fill=None):
+    """One sbce_crb on staged buffers (current stream): dict of device tensors tr_inv (B,), and by
+    ``want`` mse (B,), diag_inv (B,L); bound (B,) when ptrs carries h_true."""
+    bad = set(want) - set(_WANT_CRB) - {"bound"}
+    if bad:
+        raise ValueError(f"crb: unknown output {sorted(bad)}")
+    B, L = dims.batch, dims.n_psi * dims.n_tx
+    scratch = _scratch(torch, lib.sbce_crb_workspace_bytes, "sbce_crb_workspace_bytes",
+                       ctypes.byref(dims))
+    if scratch_fill is not None:
+        scratch.fill_(int(scratch_fill))
+    out = dict(tr_inv=torch.zeros(B, dtype=torch.float64, device="cuda"))
+    if "mse" in want or have_h:
+        out["mse"] = torch.zeros(B, dtype=torch.float64, device="cuda")
+    if "diag_inv" in want:
+        out["diag_inv"] = torch.zeros((B, L), dtype=torch.float64, device="cuda")
+    if have_h:
+        out["bound"] = torch.zeros(B, dtype=torch.float64, device="cuda")
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    opts = _lib.CrbOpts(float(sigma2), sigma2_t.data_ptr() if sigma2_t is not None else None,
+                        ptr("tr_inv"), ptr("diag_inv"), ptr("mse"), ptr("bound"),
+                        scratch.data_ptr(), scratch.numel(), 0)
+    _lib.check(lib.sbce_crb(dims, ptrs, mom.data_ptr(), opts,
+                            torch.cuda.current_stream().cuda_stream), "sbce_crb")
+    return out                         # the scratch is used in stream order: it may be freed now
+
+
+def crb_batch(y_d, y_p, psi_d, u_p, cons, n_tx, sigma2, kind="genie", m=None, S=None,
+              x_d_true=None, h_true=None, want=_WANT_CRB, ws_fill=None):
+    """Cramer-Rao bound of the cascaded-channel estimate per trial (sbce_crb, csrc/crb.hip): with
+    R = sum_p u_p u_p^H + sum_t (psi_t psi_t^H) (x) S_t the least-squares estimate with known
+    regressors has E||theta_hat - theta||^2 = n_rx sigma2 tr(R^-1), coefficient (l, r) the variance
+    sigma2 (R^-1)_ll.  kind selects the moments fed to the build:
+      "pilot"    S_t = 0: the pilot-only bound (+inf where the pilots alone do not identify the
+                 channel -- always so for signal_model's dft_n pilots -- or T_p < L)
+      "genie"    m_t = x_t, S_t = x_t x_t^H from x_d_true (B,T_d,n_tx): all data known, the floor
+                 of every semi-blind curve; finite only when T_p + T_d >= L
+      "moments"  m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx) as given (estep_batch's outputs): the
+                 complete-data error variance of the estimate made from them -- optimistic, it
+                 ignores the information lost to symbol uncertainty.
+    sigma2: the noise variance the data carry (the signal model's varn, NOT the posterior's
+    varn**2), one value or (B,).  y_d / y_p may be None (R does not depend on them; zeros are
+    staged).  h_true (B,K): also ``bound`` = mse / ||h||^2, the bound on the NMSE.
+    A trial with a Cholesky pivot not above 1e-14 max diag R is unidentifiable: every output +inf and
+    SBCE_STATUS_NONHPD in ``status``.  ws_fill: a byte the workspace and scratch are filled with first (tests).
+    Returns dict(tr_inv (B,), status (B,) [, mse (B,), diag_inv (B,L), bound (B,)]) as numpy arrays."""
+    if kind not in ("genie", "pilot", "moments"):
+        raise ValueError(f"crb_batch: unknown kind {kind!r}")
+    n_tx = int(n_tx)
+    B, T_d, P = np.shape(psi_d)
+    L = P * n_tx
+    if np.shape(u_p)[2] != L:
+        raise ValueError("u_p width must be P*n_tx")
+    if kind == "genie":
+        if x_d_true is None:
+            raise ValueError("crb_batch: kind 'genie' needs x_d_true")
+        m, S = genie_moments(np.asarray(x_d_true).reshape(B, T_d, n_tx))
+    elif kind == "pilot":
+        m, S = np.zeros((B, T_d, n_tx), dtype=complex), np.zeros((B, T_d, n_tx, n_tx), dtype=complex)
+    elif m is None or S is None:
+        raise ValueError("crb_batch: kind 'moments' needs m and S")
+    if np.shape(m) != (B, T_d, n_tx) or np.shape(S) != (B, T_d, n_tx, n_tx):
+        raise ValueError("crb_batch: m must be (B,T_d,n_tx) and S (B,T_d,n_tx,n_tx)")
+    if y_d is not None:
+        n_rx = np.shape(y_d)[2]
+    elif y_p is not None:
+        n_rx = np.shape(y_p)[2]
+    else:
+        n_rx = np.shape(h_true)[1] // L if h_true is not None else 1
+    T_p = np.shape(u_p)[1]
+    if y_d is None:
+        y_d = np.zeros((B, T_d, n_rx), dtype=complex)
+    if y_p is None:
+        y_p = np.zeros((B, T_p, n_rx), dtype=complex)
+    torch = _torch()
+    lib = _lib.load()
+    s2, s2t = _varn_arg(torch, sigma2, B)
+    st = _Staged(torch, y_d, y_p, psi_d, u_p, cons, np.zeros((B, L * n_rx), dtype=complex), 1.0,
+                 solve=_lib.SBCE_SOLVE_CHOL)
+    if ws_fill is not None:
+        st.ws.fill_(int(ws_fill))
+    mom = _dev(torch, np.concatenate([np.asarray(m).reshape(B, T_d, n_tx),
+                                      np.asarray(S).reshape(B, T_d, n_tx * n_tx)], axis=2),
+               np.complex128)
+    Ht = _cdev(torch, h_true)
+    out = _crb_call(torch, lib, st.dims, st.ptrs(h_true=Ht), mom, s2, s2t, Ht is not None,
+                    tuple(want), ws_fill)
+    out["status"] = st.status
+    torch.cuda.current_stream().synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()
+            if k in want or k in ("tr_inv", "status", "bound")}
+
+
 class EMEngine:
     """Pre-allocated device state for repeated batched EM runs (benchmark / sweeps).
 
@@ -1321,6 +1425,44 @@ class EMEngine:
     def nmse(self):
         """Per-trial NMSE of the current theta against h (device, sbce_nmse)."""
         return nmse_batch(self.theta, self.h)
+
+    def crb(self, kind="em", sigma2=None, want=_WANT_CRB, return_device=False):
+        """One sbce_crb on the engine's resident buffers (crb_batch's outputs; the workspace's R is
+        overwritten, theta is not).  kind: "em" -- the moments of one E-step (the engine's mode) at
+        the CURRENT theta, left in ``self.mom``: the complete-data error variance of the estimate
+        the next M-step would make, a truth-free and optimistic predictor of its error; "genie" --
+        all data known (needs x_d_true); "pilot" -- pilots only.  sigma2: the noise variance the
+        data carry, one value or (B,); default the engine's varn (per trial when it has them).
+        ``bound`` is returned when the engine holds the true channel."""
+        torch = self.torch
+        if kind == "em":
+            self.estep()
+            mom = self.mom
+        elif kind == "genie":
+            if self.x_d is None:
+                raise ValueError("crb('genie') needs the engine's x_d_true")
+            x = self.x_d.reshape(self.B, self.T_d, self.n_tx)
+            S = x[..., :, None] * x[..., None, :].conj()
+            mom = torch.cat([x, S.reshape(self.B, self.T_d, -1)], dim=2).contiguous()
+        elif kind == "pilot":
+            mom = torch.zeros_like(self.mom)
+        else:
+            raise ValueError(f"crb: unknown kind {kind!r}")
+        if sigma2 is None:
+            s2, s2t = self.varn, self.varn_t
+        else:
+            s2, s2t = _varn_arg(torch, sigma2, self.B)
+        ptrs = _lib.Ptrs.from_buffer_copy(self.ptrs)
+        if self.h is not None:
+            ptrs.h_true = self.h.data_ptr()
+        self._minnorm_ws = False                       # R is rebuilt
+        out = _crb_call(torch, self.lib, self.dims, ptrs, mom, s2, s2t, self.h is not None,
+                        tuple(want))
+        out["status"] = self.status
+        if return_device:
+            return out
+        torch.cuda.current_stream().synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     def minnorm_rank(self):
         """(B, 3) int32: active extent, rank of G and whether the refinement step ran, of the

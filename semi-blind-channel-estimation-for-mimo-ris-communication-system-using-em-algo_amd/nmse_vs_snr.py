@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--detectors", nargs="+", default=None,
                     help="subset of pm_soft hard zf mmse soft (default: all five), or the soft "
                          "E-steps for up to 8 streams: mmse_soft zf_soft ep")
+    ap.add_argument("--bounds", action="store_true",
+                    help="also draw the Cramer-Rao bound with all data known (crb_genie)")
     ap.add_argument("--no-replay", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -31,8 +33,9 @@ def main():
     x, curves = pkg.sweeps.nmse_vs_snr(tuple(a.SNR), a.T_d, a.T_p, a.N, a.n_rx, a.n_tx, a.itera,
                                        a.monte_iter, a.M, a.power, a.seed, replay=not a.no_replay,
                                        modes=tuple(a.detectors or pkg.sweeps.SNR_DEFAULT_MODES),
-                                       partition_r=a.partition_r)
+                                       partition_r=a.partition_r, bounds=a.bounds)
     labels = {k: v[2] for k, v in pkg.sweeps.SNR_DETECTORS.items()}
+    labels["crb_genie"] = "CRB, data known"
     report("SNR", x, {labels[k]: v for k, v in curves.items()}, a.out,
            "Proposed method with detectors")
 

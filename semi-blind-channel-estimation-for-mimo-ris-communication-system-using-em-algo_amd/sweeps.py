@@ -39,7 +39,8 @@ import numpy as np
 from . import signal_model as sm
 from .distributed import Accumulators, shard
 from .em import (em_batch, em_approx_batch, ser_batch, gauss_expand_batch, nmse_batch,
-                 detect_batch, detect_linear_batch, em_batch_noise, em_batch_conv, _GAUSS_CONS)
+                 detect_batch, detect_linear_batch, em_batch_noise, em_batch_conv, _GAUSS_CONS,
+                 crb_batch)
 from .qam import qam_constellation, gray_labeling
 
 
@@ -228,7 +229,7 @@ def _snr_groups(points, varns, batch_snr):
 
 def nmse_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2, itera=5,
                 monte_iter=15, M=4, power=10.0, seed=0, replay=True, modes=SNR_DEFAULT_MODES,
-                varh=1.0, partition_r=1, return_status=False, batch_snr=True):
+                varh=1.0, partition_r=1, return_status=False, batch_snr=True, bounds=False):
     """Mean NMSE per SNR of the five EMs of PMd/SNR/all_Detectors.py (driver :362-395; varn =
     power / 10^(SNR/10), :351-354): em_pm (r = 1), em_ml, em_zf, em_mmse and the exact em, each
     with that script's own early-stop pattern (SNR_DETECTORS) and np.linalg.solve M-step.
@@ -239,14 +240,30 @@ def nmse_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2
     variances; batch_snr=False: one call per (SNR point, detector), the same results); the
     accumulators of every (detector, SNR) point are all-reduced ONCE at the end.  Returns (SNR, {mode: curve});
     with return_status also {mode: (len(SNR),) count of trials whose status word is non-zero
-    (e.g. SBCE_STATUS_DETECTOR: the reference's nearest_symbol_ecul would raise IndexError)}."""
+    (e.g. SBCE_STATUS_DETECTOR: the reference's nearest_symbol_ecul would raise IndexError)}.
+
+    bounds=True: the curves also carry "crb_genie", the mean over trials of the Cramer-Rao bound on
+    the NMSE with all data known (em.crb_batch kind "genie", sigma2 = the point's varn): the floor
+    the semi-blind curves approach at high SNR.  It rides in the same accumulators and the one
+    all-reduce; it is +inf when any trial of the point is unidentifiable (T_p + T_d < L), and
+    return_status then also counts those trials under "crb_genie"."""
     dist, world, rank = _dist()
     mine = shard(monte_iter, world, rank).tolist()
     points, varns = gen_snr(SNR, T_d, T_p, N, n_rx, n_tx, monte_iter, M, power, seed, replay,
                             varh, keep=mine)
     cons = qam_constellation(M)
     nm, ns = len(modes), len(SNR)
-    acc = Accumulators(nm * ns, n_extra=1)
+    acc = Accumulators(nm * ns + (ns if bounds else 0), n_extra=1)
+    if bounds:
+        for k, trials in enumerate(points):
+            if not trials:
+                continue
+            b = _pack(trials, None)
+            r = crb_batch(None, None, b["psi_d"], b["u_p"], cons, n_tx, varns[k], kind="genie",
+                          x_d_true=np.stack([t["X_d"] for t in trials]), h_true=b["h"],
+                          want=("tr_inv",))
+            acc.add(nm * ns + k, r["bound"],
+                    extra_values=(r["status"] != 0).astype(float)[:, None])
     for ks, counts, b, vn in _snr_groups(points, varns, batch_snr):
         for mi, mode in enumerate(modes):
             stop = SNR_DETECTORS[mode][1]
@@ -259,11 +276,16 @@ def nmse_vs_snr(SNR=(-5, 0, 5, 10, 15, 20), T_d=50, T_p=12, N=10, n_rx=2, n_tx=2
             for k, o0, o1 in zip(ks, off[:-1], off[1:]):
                 acc.add(mi * ns + k, err[o0:o1], extra_values=flag[o0:o1])
     acc.allreduce(dist)                   # the sweep's only collective
-    mean = acc.mean_nmse().reshape(nm, ns)
+    mean = acc.mean_nmse()[:nm * ns].reshape(nm, ns)
     curves = {mode: mean[mi] for mi, mode in enumerate(modes)}
+    if bounds:
+        curves["crb_genie"] = acc.mean_nmse()[nm * ns:]
     if return_status:
-        flagged = acc.extra[:, 0].reshape(nm, ns)
-        return np.asarray(SNR), curves, {mode: flagged[mi] for mi, mode in enumerate(modes)}
+        flagged = acc.extra[:nm * ns, 0].reshape(nm, ns)
+        status = {mode: flagged[mi] for mi, mode in enumerate(modes)}
+        if bounds:
+            status["crb_genie"] = acc.extra[nm * ns:, 0]
+        return np.asarray(SNR), curves, status
     return np.asarray(SNR), curves
 
 
