@@ -693,6 +693,64 @@ int sbce_crb_workspace_bytes(const sbce_dims* d, size_t* bytes);
 int sbce_crb(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
              const sbce_crb_opts* o, void* hip_stream);
 
+/* ---- Soft-input EP detection and code-aided EM: a-priori bit L-values (an additive extension of
+ * ABI 7: no existing struct or entry point changes).  Every E-step and detector above assumes
+ * equiprobable data symbols; the three calls below take what a decoder hands back to the front
+ * end, la [B][T_d][n_tx][log2 M] float64 with La = log(P(bit = 0) / P(bit = 1)) -- the sign
+ * convention of the llr outputs -- and bit_i(s) = (labels[s] >> i) & 1.  On load each value is
+ * sanitised: NaN becomes 0 and anything outside +-64 (kPriorClamp) is clamped to +-64, so +-inf
+ * means a known bit.
+ * Per (b, t), with H, G, u, s2 and es as for SBCE_ESTEP_EP / SBCE_LINEAR_EP:
+ *   prior   lp_a[s] = -sum_i bit_i(s) La[a][i], shifted so that its largest member is 0;
+ *           pi_a = softmax(lp_a) (formed max-shifted: one weight is 1); prior mean
+ *           xbar_a = sum pi cons, prior variance v0_a = max(sum pi |cons|^2 - |xbar_a|^2,
+ *           kEpVarFloor es)
+ *   start   r_a = s2 / v0_a,  q_a = s2 xbar_a / v0_a
+ *   pass l = 1..p   the solve, the pivot rule and the cavity (t_a, h2_a) are those of
+ *           SBCE_ESTEP_EP; the demapper weights are e^{-|t_a - cons[s]|^2 / h2_a + lp_a[s]},
+ *           shifted by the largest exponent so that one weight is 1; the state update is
+ *           unchanged: v = max(s_a - |m_a|^2, floor), r' = s2 (1/v - 1/h2), q' = s2 (m/v - t/h2),
+ *           damping 0.5, kept when r' is not finite and positive
+ *   outputs of the last pass   x_soft = t and nu = h2: the extrinsic estimate (stream a's own
+ *           prior is not in them); post = the a-posteriori pmf, prior included; moments in the
+ *           product form, from post (what the E-step stores); idx_hat = argmax_s (-d_s / h2 +
+ *           lp[s]), ties to the lowest s, x_hat = cons[idx_hat]; llr[a][i] = L_post - La (the
+ *           sanitised value), the EXTRINSIC L-value, L_post the class log-sum difference over the
+ *           prior-weighted exponents (SBCE_DETECT_MAXLOG: the max-log form of the same exponents,
+ *           minus La); err is counted as in sbce_detect_linear.
+ * One pass (p = 1) is the classical soft-interference-cancellation MMSE turbo detector.
+ * Degenerate cases: a failed pivot in any pass makes every stream of the symbol channel-blind:
+ * x_soft = 0, nu = +inf, post = pi_a, moments from pi_a, llr = 0, and the status bit of the
+ * prior-free call; a stream with mu_a <= 0 gets the same for itself alone.  Every output stays
+ * finite for any s2 > 0 and any bit pattern of la.
+ * Determinism: summation orders are fixed by (n_tx, n_rx, n_psi, m, p); trial b of a B-trial call
+ * is bitwise the B = 1 call; there are no floating-point atomics.
+ * No prior (la == NULL, or pr == NULL): each call IS the existing call -- sbce_detect_linear,
+ * sbce_estep, sbce_em / sbce_em_noise / sbce_em_conv -- with the same launches and the same bits.
+ * With a prior only SBCE_LINEAR_EP and SBCE_ESTEP_EP are accepted (pass counts carried as there);
+ * any other kind or mode, and cv->ll_hist together with a prior, is SBCE_EUNSUPPORTED.
+ * SBCE_EINVAL, decided before any HIP call: la without labels, a misaligned la (8 bytes) or labels
+ * (4 bytes), flags != 0, p->x_sup set, and every check of the wrapped call.
+ * No allocation, no synchronisation; capturable in a HIP graph as a linear chain of kernel nodes;
+ * the launch counts are those of the prior-free call. */
+typedef struct sbce_prior_opts {
+    const double*  la;      /* [B][T_d][n_tx][log2 M]; NULL: no prior */
+    const int32_t* labels;  /* [M], a permutation of 0..M-1; required when la is set */
+    int32_t flags;          /* 0 */
+} sbce_prior_opts;
+
+/* sbce_detect_linear with the prior la; the labelling is p->labels. */
+int sbce_detect_linear_prior(const sbce_linear_dims* d, const sbce_linear_ptrs* p,
+                             const double* la, void* hip_stream);
+/* sbce_estep with the prior pr. */
+int sbce_estep_prior(const sbce_dims* d, const sbce_ptrs* p, int estep_mode,
+                     const sbce_prior_opts* pr, void* moments, void* hip_stream);
+/* sbce_em (nz == NULL, cv == NULL), sbce_em_noise (nz) or sbce_em_conv (cv, nz may be NULL) with
+ * the prior pr, constant over the iterations. */
+int sbce_em_prior(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+                  const sbce_prior_opts* pr, const sbce_noise_opts* nz, const sbce_conv_opts* cv,
+                  void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

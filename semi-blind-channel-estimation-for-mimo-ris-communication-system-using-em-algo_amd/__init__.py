@@ -15,7 +15,7 @@ from .em import (  # noqa: F401
     mstep_batch, nmse_batch, EMEngine, EM_Gaussian_proposed, gauss_expand_batch,
     gaussian_regressors, reduce_gaussian_channel, em_approx_batch, EM_approx,
     detect_batch, detect, em_batch_noise, noise_var_batch, loglik_batch, em_batch_conv,
-    detect_linear_batch, detect_linear, crb_batch, genie_moments,
+    detect_linear_batch, detect_linear, crb_batch, genie_moments, detect_linear_prior_batch,
 )
 
 __all__ = ["em", "em_ml", "em_llf", "em_ml_llf", "em_ml_ser", "em_pm", "em_pm_soft", "em_zf",
@@ -23,4 +23,5 @@ __all__ = ["em", "em_ml", "em_llf", "em_ml_llf", "em_ml_ser", "em_pm", "em_pm_so
            "em_zero_init", "em_batch", "em_approx_batch", "EM_approx",
            "detect_batch", "detect", "em_batch_noise", "noise_var_batch",
            "loglik_batch", "em_batch_conv", "detect_linear_batch", "detect_linear",
+           "detect_linear_prior_batch",
            "crb_batch", "genie_moments", "SbceUnavailable", "SbceError", "qam", "signal_model"]

@@ -57,7 +57,8 @@ EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_loglik_workspace_bytes", "sbce_loglik", "sbce_conv_workspace_bytes",
             "sbce_em_conv",
             "sbce_detect_linear_workspace_bytes", "sbce_detect_linear",
-            "sbce_crb_workspace_bytes", "sbce_crb")
+            "sbce_crb_workspace_bytes", "sbce_crb",
+            "sbce_detect_linear_prior", "sbce_estep_prior", "sbce_em_prior")
 
 
 class SbceUnavailable(RuntimeError):
@@ -155,6 +156,11 @@ class CrbOpts(ctypes.Structure):
                 ("mse", ctypes.c_void_p), ("bound", ctypes.c_void_p),
                 ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
                 ("flags", ctypes.c_int32)]
+
+
+class PriorOpts(ctypes.Structure):
+    """sbce_prior_opts (include/sbce.h): a-priori bit L-values of sbce_estep_prior / sbce_em_prior."""
+    _fields_ = [("la", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("flags", ctypes.c_int32)]
 
 
 _lib = None
@@ -257,6 +263,17 @@ def load(path=None):
     lib.sbce_crb.restype = ctypes.c_int
     lib.sbce_crb.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_void_p,
                              ctypes.POINTER(CrbOpts), ctypes.c_void_p]
+    lib.sbce_detect_linear_prior.restype = ctypes.c_int
+    lib.sbce_detect_linear_prior.argtypes = [ctypes.POINTER(LinearDims), ctypes.POINTER(LinearPtrs),
+                                             ctypes.c_void_p, ctypes.c_void_p]
+    lib.sbce_estep_prior.restype = ctypes.c_int
+    lib.sbce_estep_prior.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
+                                     ctypes.POINTER(PriorOpts), ctypes.c_void_p, ctypes.c_void_p]
+    lib.sbce_em_prior.restype = ctypes.c_int
+    lib.sbce_em_prior.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ptrs), ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.POINTER(PriorOpts),
+                                  ctypes.POINTER(NoiseOpts), ctypes.POINTER(ConvOpts),
+                                  ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

@@ -347,6 +347,20 @@ int check_conv(const sbce_ptrs* p, const sbce_conv_opts* cv, const Problem& pb) 
     return SBCE_OK;
 }
 
+// sbce_prior_opts (sbce_estep_prior, sbce_em_prior) after the wrapped call's own checks; *on = a
+// prior is given.  pr == NULL or la == NULL: the call is the wrapped call.
+int check_prior(const sbce_ptrs* p, const sbce_prior_opts* pr, int estep_mode, bool* on) {
+    *on = false;
+    if (!pr) return SBCE_OK;
+    if (pr->flags != 0) return SBCE_EINVAL;
+    if (!pr->la) return SBCE_OK;
+    if (!pr->labels || ((uintptr_t)pr->la & 7) || ((uintptr_t)pr->labels & 3)) return SBCE_EINVAL;
+    if (p->x_sup) return SBCE_EINVAL;
+    if (estep_mode != SBCE_ESTEP_EP) return SBCE_EUNSUPPORTED;
+    *on = true;
+    return SBCE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -393,6 +407,7 @@ struct EmChain {
     const sbce_ptrs* p = nullptr;
     const sbce_noise_opts* nz = nullptr;
     const sbce_conv_opts* cv = nullptr;
+    const sbce_prior_opts* pr = nullptr;     // a-priori L-values of the data symbols, or null
     int iters = 0, estep_mode = 0, solve_mode = 0;
     hipStream_t s = nullptr;
     Problem pb;
@@ -415,7 +430,8 @@ struct EmChain {
     int32_t rep_gen = 0;
 
     int check(const sbce_dims* d, const sbce_ptrs* p_, int iters_, int estep_mode_, int solve_mode_,
-              const sbce_noise_opts* nz_, const sbce_conv_opts* cv_, void* hip_stream) {
+              const sbce_noise_opts* nz_, const sbce_conv_opts* cv_, void* hip_stream,
+              const sbce_prior_opts* pr_ = nullptr) {
         p = p_; nz = nz_; cv = cv_;
         iters = iters_; estep_mode = estep_mode_; solve_mode = solve_mode_;
         s = (hipStream_t)hip_stream;
@@ -438,6 +454,10 @@ struct EmChain {
             return SBCE_EINVAL;
         if (nz && (rc = check_noise(p, nz, pb))) return rc;
         if (cv && (rc = check_conv(p, cv, pb))) return rc;
+        bool prior;
+        if ((rc = check_prior(p, pr_, estep_mode, &prior))) return rc;
+        if (prior && cv && cv->ll_hist) return SBCE_EUNSUPPORTED;   // sbce_loglik has no prior
+        pr = prior ? pr_ : nullptr;
         empty = pb.B == 0 || iters == 0;
         c = carve(pb, solve_mode);
         ws = (char*)p->workspace;
@@ -480,6 +500,10 @@ struct EmChain {
 
         ea = estep_args(p, ws + c.mom, ws, &c);
         ea.done = (early || cv || freeze) ? done : nullptr;
+        if (pr) {                            // constant within the call: the chain stays a pure
+            ea.la = pr->la;                  // function of theta per trial
+            ea.labels = pr->labels;
+        }
         if (nz) {                            // the estimate starts at the caller's parameter
             if ((rc = hip_rc(launch_noise_init(pb.B, nz->varn_est, p->varn_t, pb.varn, s))))
                 return rc;
@@ -584,10 +608,11 @@ struct EmChain {
 };
 
 int em_run(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
-           const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream) {
+           const sbce_noise_opts* nz, const sbce_conv_opts* cv, void* hip_stream,
+           const sbce_prior_opts* pr = nullptr) {
     clear_stale_error();
     EmChain ch;
-    int rc = ch.check(d, p, iters, estep_mode, solve_mode, nz, cv, hip_stream);
+    int rc = ch.check(d, p, iters, estep_mode, solve_mode, nz, cv, hip_stream, pr);
     if (rc) return rc;
     if ((rc = ch.begin())) return rc;
     for (int it = 0; it < iters; ++it)
@@ -810,6 +835,12 @@ int sbce_em_conv(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mo
     return em_run(d, p, iters, estep_mode, solve_mode, nz, cv, hip_stream);
 }
 
+int sbce_em_prior(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_mode, int solve_mode,
+                  const sbce_prior_opts* pr, const sbce_noise_opts* nz, const sbce_conv_opts* cv,
+                  void* hip_stream) {
+    return em_run(d, p, iters, estep_mode, solve_mode, nz, cv, hip_stream, pr);
+}
+
 int sbce_loglik_workspace_bytes(const sbce_dims* d, size_t* bytes) {
     Problem pb;
     if (!bytes || !make_problem(d, pb)) return SBCE_EINVAL;
@@ -858,6 +889,11 @@ int sbce_noise_var(const sbce_dims* d, const sbce_ptrs* p, const void* moments,
 
 int sbce_estep(const sbce_dims* d, const sbce_ptrs* p, int estep_mode, void* moments,
                void* hip_stream) {
+    return sbce_estep_prior(d, p, estep_mode, nullptr, moments, hip_stream);
+}
+
+int sbce_estep_prior(const sbce_dims* d, const sbce_ptrs* p, int estep_mode,
+                     const sbce_prior_opts* pr, void* moments, void* hip_stream) {
     clear_stale_error();
     Problem pb;
     if (linear_oversize(d, estep_mode)) return SBCE_EUNSUPPORTED;
@@ -868,12 +904,18 @@ int sbce_estep(const sbce_dims* d, const sbce_ptrs* p, int estep_mode, void* mom
     if (!moments || !aligned16(moments)) return SBCE_EINVAL;
     if (estep_mode == SBCE_ESTEP_GAUSS && !(pb.varx > 0.0)) return SBCE_EINVAL;
     if (!estep_supported(pb, estep_mode)) return SBCE_EUNSUPPORTED;
+    bool prior;
+    if ((rc = check_prior(p, pr, estep_mode, &prior))) return rc;
     if (pb.B == 0) return SBCE_OK;
     if ((rc = status_init(p->status, pb.B, (hipStream_t)hip_stream))) return rc;
     // workspace optional here: use it when it is large enough (the E-step regions come first)
     const Carve c = carve(pb, SBCE_SOLVE_CHOL);
     const bool use_ws = p->workspace && aligned16(p->workspace) && p->workspace_bytes >= c.total;
-    const EstepArgs ea = estep_args(p, moments, (char*)p->workspace, use_ws ? &c : nullptr);
+    EstepArgs ea = estep_args(p, moments, (char*)p->workspace, use_ws ? &c : nullptr);
+    if (prior) {
+        ea.la = pr->la;
+        ea.labels = pr->labels;
+    }
     return hip_rc(launch_estep(pb, ea, estep_mode, (hipStream_t)hip_stream));
 }
 
@@ -1209,6 +1251,11 @@ int sbce_detect_linear_workspace_bytes(const sbce_linear_dims* d, size_t* bytes)
 }
 
 int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, void* hip_stream) {
+    return sbce_detect_linear_prior(d, p, nullptr, hip_stream);
+}
+
+int sbce_detect_linear_prior(const sbce_linear_dims* d, const sbce_linear_ptrs* p, const double* la,
+                             void* hip_stream) {
     if (!d || !p) return SBCE_EINVAL;
     if (d->batch < 1 || d->n_tx < 1 || d->n_rx < 1 || d->n_psi < 1 || d->t_d < 1 ||
         !(d->sigma2 > 0.0))
@@ -1240,6 +1287,10 @@ int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, voi
     sbce_detect_linear_workspace_bytes(d, &need);
     if (need && (!p->workspace || !aligned16(p->workspace))) return SBCE_EINVAL;
     if (p->workspace_bytes < need) return SBCE_EWORKSPACE;
+    if (la) {                            // the prior's own checks, after the wrapped call's
+        if (!p->labels || ((uintptr_t)la & 7)) return SBCE_EINVAL;
+        if (d->kind != SBCE_LINEAR_EP) return SBCE_EUNSUPPORTED;
+    }
     clear_stale_error();
     LinearArgs a{};                      // lgM and chunks are launch_detect_linear's
     a.yd = (const cd*)p->y_d; a.psid = (const cd*)p->psi_d; a.cons = (const cd*)p->cons;
@@ -1252,7 +1303,8 @@ int sbce_detect_linear(const sbce_linear_dims* d, const sbce_linear_ptrs* p, voi
     a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0;
     a.passes = ep_passes_of(ep_word);
     a.sigma2 = d->sigma2; a.es = d->es;
-    return hip_rc(launch_detect_linear(a, (hipStream_t)hip_stream));
+    return hip_rc(la ? launch_detect_linear_prior(a, la, (hipStream_t)hip_stream)
+                     : launch_detect_linear(a, (hipStream_t)hip_stream));
 }
 
 }  // extern "C"

@@ -37,7 +37,7 @@
 // variance of the last pass; everything after them is the same code.  The MMSE / ZF instantiation
 // keeps its statements in their former order and LinearArgs its former offsets (the new field is
 // last): its instructions are those of the kernel before the EP flag.
-#include "ep_solve.h"
+#include "ep_prior.h"
 
 namespace sbce {
 
@@ -199,6 +199,162 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
     }
 }
 
+// sbce_detect_linear_prior: the EP instantiation above with a-priori bit L-values
+// la [B][Td][NT][lgM] -- the passes start from the prior's moments and every demapper weight
+// carries the point's a-priori probability (ep_prior.h).  A kernel of its own, so that the
+// instantiations above keep their instructions.  x_soft = t and nu = h2 are the extrinsic
+// estimate of the last pass; post, the moments and the decision are a-posteriori (exponent
+// -d_s / h2 + lp[s], the decision its argmax with ties to the lowest s); llr = L_post - La is
+// extrinsic.  A dead stream (failed symbol, or mu <= 0) has x_soft = 0, nu = +inf, post = the
+// a-priori pmf and llr = 0.
+template <int NT>
+__global__ __launch_bounds__(kLinThreads, 3) void detect_linear_prior_kernel(LinearArgs a,
+                                                                             const double* la) {
+    __shared__ cd buf_s[kLinBuf];
+    __shared__ cd cons_s[64];
+    __shared__ int lab_s[64];
+    __shared__ int cnt_s[3];        // symbol errors, bit errors, failed-pivot flag
+
+    const int NR = a.NR, P = a.P, Td = a.Td, M = a.M, lgM = a.lgM;
+    const int NE = NT * NR;
+    const int b = blockIdx.x / a.chunks, ch = blockIdx.x % a.chunks;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int t0 = ch * kLinSym;
+    const int tend = t0 + kLinSym < Td ? t0 + kLinSym : Td;
+    const size_t bt = (size_t)b * Td;
+
+    if (tid < M) {
+        cons_s[tid] = a.cons[tid];
+        lab_s[tid] = a.labels[tid];
+    }
+    if (tid < 3) cnt_s[tid] = 0;
+
+    lin_stage_h(buf_s, a.theta + (size_t)b * P * NE, a.psid + bt * P, NE, P, t0, tend);
+
+    const int grp = lane >> 3, al = lane & 7;
+    const int ts = t0 + w * 8 + grp;
+    const bool act = al < NT && ts < tend;
+    const int aa = al < NT ? al : 0;
+    const int k = ts < tend ? w * 8 + grp : tend - 1 - t0;
+    const size_t sym = bt + t0 + k;
+    const double s2 = a.sigma2_t ? a.sigma2_t[b] : a.sigma2;
+    const size_t o = sym * NT + aa;
+
+    const EpPrior pr = ep_prior_load(la + o * lgM, lgM);
+    cd xs;
+    double nu, inv;
+    bool dead, fail;
+    {
+        cd c0[NT + 1];
+        ep_gram<NT>(buf_s + k * kLinHS, a.yd + sym * NR, NR, aa, c0);
+        ep_prior_run<NT>(c0, cons_s, lab_s, M, lgM, pr, s2, a.es, a.passes, aa, lane, xs, nu, inv,
+                         dead, fail);
+    }
+
+    // ---- demap of stream a: the largest exponent, its index and the per-bit-class maxima, then
+    // the max-shifted sums (the largest member of every sum has weight 1: nothing is 0/0)
+    double emax = -INFINITY;
+    int idx = 0;
+    double m0[6], m1[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) m0[i] = m1[i] = -INFINITY;
+    for (int s = 0; s < M; ++s) {
+        const int lb = lab_s[s];
+        const double e = ep_prior_exponent(pr, cons_s[s], lb, lgM, xs, inv);
+        if (e > emax) {
+            emax = e;
+            idx = s;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const bool one = (lb >> i) & 1;
+            m0[i] = one ? m0[i] : fmax(m0[i], e);
+            m1[i] = one ? fmax(m1[i], e) : m1[i];
+        }
+    }
+    double Z = 0.0, saa = 0.0;
+    cd mean = czero();
+    double T0[6], T1[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) T0[i] = T1[i] = 0.0;
+    for (int s = 0; s < M; ++s) {
+        const cd cs = cons_s[s];
+        const int lb = lab_s[s];
+        const double ex = ep_prior_exponent(pr, cs, lb, lgM, xs, inv);
+        const double e = fexp_neg(ex - emax);
+        Z += e;
+        mean = caxpy(mean, e, cs);
+        saa = fma(e, cabs2(cs), saa);
+        if (a.llr && !a.maxlog) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                if (i < lgM) {
+                    const bool one = (lb >> i) & 1;
+                    const double ec = fexp_neg(ex - (one ? m1[i] : m0[i]));
+                    T0[i] = one ? T0[i] : T0[i] + ec;
+                    T1[i] = one ? T1[i] + ec : T1[i];
+                }
+            }
+        }
+    }
+    mean = cmk(mean.x / Z, mean.y / Z);
+    saa /= Z;
+
+    if (act) {
+        if (a.xsoft) a.xsoft[o] = xs;
+        if (a.nu) a.nu[o] = nu;
+        if (a.xhat) a.xhat[o] = cons_s[idx];
+        if (a.idx) a.idx[o] = idx;
+        if (a.post)
+            for (int s = 0; s < M; ++s)
+                a.post[o * M + s] =
+                    fexp_neg(ep_prior_exponent(pr, cons_s[s], lab_s[s], lgM, xs, inv) - emax) / Z;
+        if (a.llr) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+                if (i < lgM) {
+                    double l = m0[i] - m1[i];
+                    if (!a.maxlog) l += log(T0[i]) - log(T1[i]);
+                    a.llr[o * lgM + i] = dead ? 0.0 : l - ep_prior_la(pr, i);
+                }
+        }
+        if (a.err) {
+            const cd xt = a.xd[o];
+            double bd = INFINITY;
+            int bi = 0;
+            for (int s = 0; s < M; ++s) {
+                const double dx = cabs2(csub(cons_s[s], xt));
+                if (dx < bd) {
+                    bd = dx;
+                    bi = s;
+                }
+            }
+            if (bi != idx) {
+                atomicAdd(&cnt_s[0], 1);
+                atomicAdd(&cnt_s[1], __popc((unsigned)(lab_s[bi] ^ lab_s[idx])));
+            }
+        }
+        if (fail) cnt_s[2] = 1;
+    }
+    if (a.mom) {                     // uniform: the cross-lane moves see every lane
+        cd* mo = a.mom + sym * (NT + NT * NT);
+        if (act) mo[aa] = mean;
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            const cd mq = bperm_c(mean, ((lane & 56) | q) << 2);
+            if (act) mo[NT + aa * NT + q] = q == aa ? cmk(saa, 0.0) : cmulc(mean, mq);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        if (a.err && (cnt_s[0] | cnt_s[1])) {
+            atomicAdd(&a.err[2 * b], cnt_s[0]);
+            atomicAdd(&a.err[2 * b + 1], cnt_s[1]);
+        }
+        if (a.status && cnt_s[2]) atomicOr(&a.status[b], SBCE_STATUS_NONHPD);
+    }
+}
+
 // err[b][0..1] = 0 and status[b] = 0 (each when set) ahead of the detection kernel's integer adds
 // and ORs.  A kernel, not hipMemsetAsync: in the graph-capture test the memset nodes of this call
 // were observed to leave stale words in err and status on replay (HIP 7.0 runtime; the cause is
@@ -210,8 +366,11 @@ __global__ __launch_bounds__(256) void linear_zero_kernel(int32_t* err, int32_t*
 }
 
 template <int NT>
-hipError_t launch_nt(const LinearArgs& a, hipStream_t s) {
-    if (a.kind == SBCE_LINEAR_EP)
+hipError_t launch_nt(const LinearArgs& a, const double* la, hipStream_t s) {
+    if (la)
+        hipLaunchKernelGGL(detect_linear_prior_kernel<NT>, dim3((unsigned)(a.B * a.chunks)),
+                           dim3(kLinThreads), 0, s, a, la);
+    else if (a.kind == SBCE_LINEAR_EP)
         hipLaunchKernelGGL((detect_linear_kernel<NT, true>), dim3((unsigned)(a.B * a.chunks)),
                            dim3(kLinThreads), 0, s, a);
     else
@@ -225,6 +384,11 @@ hipError_t launch_nt(const LinearArgs& a, hipStream_t s) {
 bool detect_linear_supported(int NT, int NR) { return NT >= 1 && NT <= 8 && NR >= 1 && NR <= 8; }
 
 hipError_t launch_detect_linear(LinearArgs a, hipStream_t s) {
+    return launch_detect_linear_prior(a, nullptr, s);
+}
+
+hipError_t launch_detect_linear_prior(LinearArgs a, const double* la, hipStream_t s) {
+    if (la && (a.kind != SBCE_LINEAR_EP || !a.labels)) return hipErrorInvalidValue;
     a.lgM = 0;
     while ((1 << a.lgM) < a.M) ++a.lgM;
     a.chunks = (a.Td + kLinSym - 1) / kLinSym;
@@ -236,14 +400,14 @@ hipError_t launch_detect_linear(LinearArgs a, hipStream_t s) {
         if (e != hipSuccess) return e;
     }
     switch (a.NT) {
-        case 1: return launch_nt<1>(a, s);
-        case 2: return launch_nt<2>(a, s);
-        case 3: return launch_nt<3>(a, s);
-        case 4: return launch_nt<4>(a, s);
-        case 5: return launch_nt<5>(a, s);
-        case 6: return launch_nt<6>(a, s);
-        case 7: return launch_nt<7>(a, s);
-        case 8: return launch_nt<8>(a, s);
+        case 1: return launch_nt<1>(a, la, s);
+        case 2: return launch_nt<2>(a, la, s);
+        case 3: return launch_nt<3>(a, la, s);
+        case 4: return launch_nt<4>(a, la, s);
+        case 5: return launch_nt<5>(a, la, s);
+        case 6: return launch_nt<6>(a, la, s);
+        case 7: return launch_nt<7>(a, la, s);
+        case 8: return launch_nt<8>(a, la, s);
     }
     return hipErrorInvalidValue;
 }

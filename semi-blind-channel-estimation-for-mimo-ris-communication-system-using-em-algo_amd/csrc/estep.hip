@@ -1,6 +1,6 @@
 // E-step routing: which unit computes the per-symbol posterior moments of (pb, mode).
 //   soft ZF / MMSE                 estep_linear.hip
-//   expectation propagation        estep_ep.hip
+//   expectation propagation        estep_ep.hip; with a-priori L-values estep_ep_prior.hip
 //   PM / ZF / MMSE / Gauss         estep_pm.hip
 //   exact soft / hard              the MFMA sweep (estep_sweep.hip) where one exists for the shape
 //                                  (JA, JB >= 16), behind the preparation or the sphere pass
@@ -29,7 +29,8 @@ bool estep_momfold_supported(const Problem& pb, int mode) {
 
 hipError_t launch_estep(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s) {
     if (estep_linear_mode(mode)) return launch_estep_linear(pb, a, mode, s);
-    if (mode == SBCE_ESTEP_EP) return launch_estep_ep(pb, a, s);
+    if (mode == SBCE_ESTEP_EP) return a.la ? launch_estep_ep_prior(pb, a, s) : launch_estep_ep(pb, a, s);
+    if (a.la) return hipErrorInvalidValue;   // the entry points accept a prior with EP only
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return launch_estep_pm(pb, a, mode, pb.pr, s);
     const SweepPlan sp = estep_sweep_plan(pb);
     // SBCE_ESTEP_IMPL=valu: the VALU kernel at every shape (A/B runs)

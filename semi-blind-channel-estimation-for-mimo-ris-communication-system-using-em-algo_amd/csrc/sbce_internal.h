@@ -321,6 +321,10 @@ struct EstepArgs {
     // is loaded -- iteration 0 of a call, whose mom holds stale contents, and every E-step some
     // kernel of which does not carry the fold: estep_momfold_supported)
     int32_t* mchg = nullptr;          // [B]
+    // a-priori bit L-values of the data symbols (sbce_prior_opts; SBCE_ESTEP_EP only, both set or
+    // both null): launch_estep then takes estep_ep_prior.hip's kernel
+    const double* la = nullptr;       // [B][Td][NT][log2 M]
+    const int32_t* labels = nullptr;  // [M]
 };
 
 // The fold of the moment-repeat rule at a moment store: nonzero when the value about to be stored
@@ -571,6 +575,8 @@ inline int ep_passes_of(int word) {
 }
 bool estep_ep_supported(const Problem& pb);   // the soft MMSE E-step's limits, pr in 0..16
 hipError_t launch_estep_ep(const Problem& pb, const EstepArgs& a, hipStream_t s);
+// soft-input EP E-step (estep_ep_prior.hip): EstepArgs::la and ::labels set, limits as above
+hipError_t launch_estep_ep_prior(const Problem& pb, const EstepArgs& a, hipStream_t s);
 int estep_prep_stride(const Problem& pb);   // doubles per symbol, 0 if no MFMA sweep
 // pilots_factored: launch_pilot_factor already ran for these u_p (ppsi, pS, pflag valid)
 hipError_t launch_mstep_build(const Problem& pb, const MstepArgs& a, hipStream_t s,
@@ -720,6 +726,9 @@ struct LinearArgs {
 };
 bool detect_linear_supported(int NT, int NR);   // 1..8, 1..8
 hipError_t launch_detect_linear(LinearArgs a, hipStream_t s);
+// sbce_detect_linear_prior: kind SBCE_LINEAR_EP, a.labels set, la [B][Td][NT][log2 M] the a-priori
+// bit L-values; the same two launches with the prior kernel in place of the detection kernel
+hipError_t launch_detect_linear_prior(LinearArgs a, const double* la, hipStream_t s);
 
 // Noise-variance update (noise.hip, sbce_noise_var / sbce_em_noise): two launches per update
 struct NoiseArgs {

@@ -186,9 +186,41 @@ def _result(torch, out, return_device):
     return {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
 
 
+def _prior_arg(torch, prior_llr, labels, B, T_d, n_tx, M, mode="ep"):
+    """A-priori bit L-values of a call (include/sbce.h sbce_prior_opts): (la, labels) as device
+    tensors -- la (B,T_d,n_tx,log2 M) float64, log(P(bit = 0) / P(bit = 1)), NaN / inf allowed --
+    or (None, None) without a prior.  labels=None: the package's Gray labelling."""
+    if prior_llr is None:
+        return None, None
+    if mode != "ep":
+        raise ValueError("prior_llr needs the expectation-propagation mode / kind 'ep'")
+    lgM = max(int(M - 1).bit_length(), 1)
+    if isinstance(prior_llr, torch.Tensor):
+        la = prior_llr.to(device="cuda", dtype=torch.float64).contiguous()
+    else:
+        la = _dev(torch, prior_llr, np.float64)
+    if tuple(la.shape) != (B, T_d, n_tx, lgM):
+        raise ValueError(f"prior_llr shape {tuple(la.shape)} != {(B, T_d, n_tx, lgM)}")
+    if isinstance(labels, torch.Tensor):
+        return la, labels
+    return la, torch.from_numpy(_detect_labels(M, labels, True)).to("cuda")
+
+
+class _Prior:
+    """sbce_prior_opts of a call and the tensors it points to (kept alive with it)."""
+
+    def __init__(self, la, lab):
+        self.la, self.lab = la, lab
+        self.opts = _lib.PriorOpts(la.data_ptr(), lab.data_ptr(), 0) if la is not None else None
+
+    def ref(self):
+        return ctypes.byref(self.opts) if self.opts is not None else None
+
+
 def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_true=None,
              h_true=None, solve="chol", return_device=False, partition_r=0,
-             return_decisions=False, x_sup=None, varx=1.0, ep_passes=None):
+             return_decisions=False, x_sup=None, varx=1.0, ep_passes=None, prior_llr=None,
+             labels=None):
     """Run ``itera`` EM iterations on a batch of independent trials.
 
     Array layouts (complex128, batch-major, include/sbce.h):
@@ -210,6 +242,10 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
     Gaussian-prior EM (MIMO_Gaussian_proposed.py:56-89) with prior variance parameter varx;
     psi_d then has P = N rows (no direct path), cons is ignored, theta is the reduced
     channel (gauss_expand_batch gives the reference's n_rx x Q matrix).
+    prior_llr (B,T_d,n_tx,log2 M) (mode "ep" only): a-priori bit L-values log(P(bit = 0) /
+    P(bit = 1)) of the data symbols, e.g. a decoder's feedback or qam.prior_llr_known's for known
+    symbols (sbce_em_prior: soft-input EP, the moments are a-posteriori); labels: the labelling
+    they refer to (None: Gray, as detect_batch).
     Inputs may be numpy arrays or CUDA complex128 tensors (used in place).  varn may be one
     value or one per trial ((B,) array: the trials of several SNR points in one call, include/
     sbce.h sbce_ptrs.varn_t; each trial's result is that of a call with its own varn).
@@ -227,8 +263,13 @@ def em_batch(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", x_d_t
              if return_decisions else None)
     ptrs = st.ptrs(x_d_true=Xd, llf=llf, h_true=Ht, x_dest=xdest, x_sup=Xs)
     stream = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.sbce_em(st.dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve], stream),
-               "sbce_em")
+    pr = _Prior(*_prior_arg(torch, prior_llr, labels, st.B, st.T_d, st.n_tx, st.M, mode))
+    if pr.opts is None:
+        _lib.check(lib.sbce_em(st.dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve], stream),
+                   "sbce_em")
+    else:
+        _lib.check(lib.sbce_em_prior(st.dims, ptrs, int(itera), _MODES[mode], _SOLVES[solve],
+                                     pr.ref(), None, None, stream), "sbce_em_prior")
     out = dict(theta=st.theta, llf=llf, status=st.status, iters_done=st.iters_done)
     if xdest is not None:
         out["x_dest"] = xdest
@@ -290,13 +331,14 @@ def noise_var_batch(y_d, y_p, psi_d, u_p, theta, m, S, varn_min=1e-6, return_sta
 
 
 def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft", solve="chol",
-                   partition_r=0, h_true=None, varn_min=1e-6, return_device=False, ep_passes=None):
+                   partition_r=0, h_true=None, varn_min=1e-6, return_device=False, ep_passes=None,
+                   prior_llr=None, labels=None):
     """em_batch with the noise parameter unknown (sbce_em_noise): it is estimated per trial beside
     theta, on the device, inside the iteration chain -- per iteration E-step, M-step, noise update
     (csrc/noise.hip), oracle early stop.  ``varn`` (one value or (B,)) is only the START of the
     parameter; the posterior of every E-step divides by the current estimate squared, sigma^2.
     mode: "soft" | "hard" | "pm" | "pm_soft" | "zf" | "mmse" | "mmse_soft" | "zf_soft" | "ep"
-    (with ``ep_passes``, as em_batch).  varn_min:
+    (with ``ep_passes``, ``prior_llr`` and ``labels``, as em_batch).  varn_min:
     floor of the parameter (a trial that reaches it has SBCE_STATUS_NOISE set and varn == varn_min exactly).
     Returns dict(theta (B,K), varn (B,) the parameter after each trial's last update, sigma2 =
     varn**2, hist (B,itera) the parameter after each iteration (a stopped trial's later entries
@@ -314,9 +356,15 @@ def em_batch_noise(y_d, y_p, psi_d, u_p, cons, varn, itera, theta0, mode="soft",
                  solve=_SOLVES[solve], check="theta0", clone=True)
     opts, est, hist, scratch = _noise_opts(torch, lib, st, vmin, int(itera))
     Ht = _cdev(torch, h_true)
-    _lib.check(lib.sbce_em_noise(st.dims, st.ptrs(h_true=Ht), int(itera), _MODES[mode],
-                                 _SOLVES[solve], opts, torch.cuda.current_stream().cuda_stream),
-               "sbce_em_noise")
+    pr = _Prior(*_prior_arg(torch, prior_llr, labels, st.B, st.T_d, st.n_tx, st.M, mode))
+    stream = torch.cuda.current_stream().cuda_stream
+    if pr.opts is None:
+        _lib.check(lib.sbce_em_noise(st.dims, st.ptrs(h_true=Ht), int(itera), _MODES[mode],
+                                     _SOLVES[solve], opts, stream), "sbce_em_noise")
+    else:
+        _lib.check(lib.sbce_em_prior(st.dims, st.ptrs(h_true=Ht), int(itera), _MODES[mode],
+                                     _SOLVES[solve], pr.ref(), ctypes.byref(opts), None, stream),
+                   "sbce_em_prior")
     out = dict(theta=st.theta, varn=est, sigma2=est * est, hist=hist, status=st.status,
                iters_done=st.iters_done)
     return _result(torch, out, return_device)
@@ -348,7 +396,8 @@ def loglik_batch(y_d, y_p, psi_d, u_p, cons, theta, varn, n_tx, per_symbol=False
 
 def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta=1e-6, tol_ll=0.0,
                   min_iters=2, estimate_noise=False, varn_min=1e-6, loglik=False, mode="soft",
-                  partition_r=0, solve="chol", return_device=False, ep_passes=None):
+                  partition_r=0, solve="chol", return_device=False, ep_passes=None,
+                  prior_llr=None, labels=None):
     """em_batch with a per-trial stop that needs no ground truth (sbce_em_conv): a trial stops
     after iteration l (at least min_iters performed) when ||theta_l - theta_{l-1}|| <= tol_theta
     ||theta_l|| (theta_{-1} = theta0), or -- tol_ll > 0, which needs loglik=True -- when its
@@ -358,6 +407,7 @@ def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta
     log-likelihood after every iteration (one sbce_loglik pass each: a diagnostic, soft-EM shapes
     with n_tx <= 4 and M**n_tx <= 65536 only).  mode: as em_batch_noise ("mmse_soft" / "zf_soft" / "ep"
     included: the theta rule works at every n_tx, loglik=True keeps its n_tx <= 4 limit).
+    prior_llr / labels: as em_batch (mode "ep"; not together with loglik=True).
     Returns dict(theta (B,K), iters_done (B,), status (B,) with SBCE_STATUS_CONVERGED where a rule
     stopped the trial, dtheta_hist (B,max_iters) the relative step after each iteration, ll_hist
     (B,max_iters) or None, varn (B,) the parameter each trial ended with, sigma2 = varn**2, hist
@@ -395,9 +445,15 @@ def em_batch_conv(y_d, y_p, psi_d, u_p, cons, varn, max_iters, theta0, tol_theta
         est = st.varn_t
     else:
         est = torch.full((B,), st.varn, dtype=torch.float64, device="cuda")
-    _lib.check(lib.sbce_em_conv(st.dims, st.ptrs(), iters, _MODES[mode], _SOLVES[solve],
-                                ctypes.byref(nz) if nz is not None else None, ctypes.byref(cv),
-                                torch.cuda.current_stream().cuda_stream), "sbce_em_conv")
+    pr = _Prior(*_prior_arg(torch, prior_llr, labels, st.B, st.T_d, st.n_tx, st.M, mode))
+    nzr = ctypes.byref(nz) if nz is not None else None
+    stream = torch.cuda.current_stream().cuda_stream
+    if pr.opts is None:
+        _lib.check(lib.sbce_em_conv(st.dims, st.ptrs(), iters, _MODES[mode], _SOLVES[solve], nzr,
+                                    ctypes.byref(cv), stream), "sbce_em_conv")
+    else:
+        _lib.check(lib.sbce_em_prior(st.dims, st.ptrs(), iters, _MODES[mode], _SOLVES[solve],
+                                     pr.ref(), nzr, ctypes.byref(cv), stream), "sbce_em_prior")
     out = dict(theta=st.theta, iters_done=st.iters_done, status=st.status, dtheta_hist=dth,
                ll_hist=llh, varn=est, sigma2=est * est, hist=hist)
     return _result(torch, out, return_device)
@@ -568,7 +624,7 @@ def em_mmse(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, 
 
 
 def _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_initial, h, mode,
-                 solve, verbose, ep_passes=None):
+                 solve, verbose, ep_passes=None, prior_llr=None, labels=None):
     """_detector for the soft ZF / MMSE modes: all_possibleSymbols may also be the (M,) table
     itself (the M^n_tx hypothesis table is never enumerated and is out of reach at n_tx = 8);
     n_tx then follows from h_initial's length."""
@@ -585,7 +641,9 @@ def _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, aps, M, varn, itera, h_in
                             cons=aps[:int(M)])
     hh = None if h is None else np.asarray(h, dtype=complex).reshape(1, -1)
     res = em_batch(d["y_d"], d["y_p"], d["psi_d"], d["u_p"], d["cons"], varn, itera, d["theta0"],
-                   mode=mode, h_true=hh, solve=solve, ep_passes=ep_passes)
+                   mode=mode, h_true=hh, solve=solve, ep_passes=ep_passes,
+                   prior_llr=None if prior_llr is None else np.asarray(prior_llr)[None],
+                   labels=labels)
     return _finish(res, verbose, itera)
 
 
@@ -610,13 +668,14 @@ def em_mmse_soft(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, v
 
 
 def em_ep(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera, h_initial, h,
-          verbose=False, solve="chol", ep_passes=None):
+          verbose=False, solve="chol", ep_passes=None, prior_llr=None, labels=None):
     """Expectation-propagation EM for up to 8 streams (em_mmse_soft's argument list): ``ep_passes``
     passes (None: 5; 1..16) of em_mmse_soft's solve per symbol, each with the demapper's
     per-stream means and variances of the pass before as the prior (include/sbce.h
-    SBCE_ESTEP_EP); one pass is em_mmse_soft."""
+    SBCE_ESTEP_EP); one pass is em_mmse_soft.  prior_llr (T_d,n_tx,log2 M): a-priori bit
+    L-values of the data symbols with the labelling ``labels`` (None: Gray), as em_batch."""
     return _soft_linear(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
-                        h_initial, h, "ep", solve, verbose, ep_passes)
+                        h_initial, h, "ep", solve, verbose, ep_passes, prior_llr, labels)
 
 
 def em_ml_ser(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, varn, itera,
@@ -914,8 +973,9 @@ _LINEAR_KINDS = {"mmse": _lib.SBCE_LINEAR_MMSE, "zf": _lib.SBCE_LINEAR_ZF,
 
 
 def _detect_linear_call(torch, Yd, Ps, Cs, Th, n_tx, kind, sigma2, sigma2_t, es, lab, Xd, maxlog,
-                        want, ep_passes=None):
-    """One sbce_detect_linear on device tensors; returns the dict of device outputs."""
+                        want, ep_passes=None, la=None):
+    """One sbce_detect_linear (la, the a-priori L-values on the device: sbce_detect_linear_prior)
+    on device tensors; returns the dict of device outputs."""
     lib = _lib.load()
     B, T_d, n_rx = Yd.shape
     P, M = Ps.shape[2], Cs.shape[0]
@@ -959,8 +1019,12 @@ def _detect_linear_call(torch, Yd, Ps, Cs, Th, n_tx, kind, sigma2, sigma2_t, es,
                            ptr("x_soft"), ptr("nu"), ptr("x_hat"), ptr("idx"), ptr("post"),
                            ptr("llr"), ptr("err"), ptr("moments"), ptr("status"),
                            ws.data_ptr() if ws is not None else None, nb.value)
-    _lib.check(lib.sbce_detect_linear(dims, ptrs, torch.cuda.current_stream().cuda_stream),
-               "sbce_detect_linear")
+    stream = torch.cuda.current_stream().cuda_stream
+    if la is None:
+        _lib.check(lib.sbce_detect_linear(dims, ptrs, stream), "sbce_detect_linear")
+    else:
+        _lib.check(lib.sbce_detect_linear_prior(dims, ptrs, la.data_ptr(), stream),
+                   "sbce_detect_linear_prior")
     return out
 
 
@@ -989,25 +1053,50 @@ def detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind="mmse", es=Non
     nearest table point; post (B,T_d,n_tx,M) and llr (B,T_d,n_tx,log2 M) of the Gaussian demapper
     (exact or, maxlog=True, max-log); moments (B,T_d,n_tx+n_tx^2) in estep_batch's layout; status
     (B,) int32, SBCE_STATUS_NONHPD where a symbol's matrix had a failed pivot (that symbol:
-    x_soft = 0, nu = inf, post = 1/M, llr = 0); with x_d_true also err (B,2) int32."""
+    x_soft = 0, nu = inf, post = 1/M, llr = 0); with x_d_true also err (B,2) int32.
+    With a-priori bit L-values: detect_linear_prior_batch."""
+    return _detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind, es, labels, x_d_true,
+                                noise, maxlog, want, return_device, None)
+
+
+def detect_linear_prior_batch(y_d, psi_d, cons, theta, varn, n_tx, prior_llr, kind="ep", es=None,
+                              labels=None, x_d_true=None, noise="em", maxlog=False,
+                              want=_WANT_LINEAR, return_device=False):
+    """detect_linear_batch with a-priori bit L-values (sbce_detect_linear_prior, soft-input EP; a
+    function of its own because detect_linear_batch's argument list is fixed): prior_llr
+    (B,T_d,n_tx,log2 M) = log(P(bit = 0) / P(bit = 1)) under ``labels`` (None: Gray), NaN read as
+    0 and +-inf as a known bit; kind 'ep' or ('ep', p) only -- one pass is the soft-cancellation
+    MMSE turbo detector.  x_soft, nu and llr are then extrinsic (stream a's own prior is not in
+    them), post, moments and the decisions a-posteriori; a failed symbol has post = the
+    a-priori pmf and llr = 0.  prior_llr=None is detect_linear_batch."""
+    return _detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind, es, labels, x_d_true,
+                                noise, maxlog, want, return_device, prior_llr)
+
+
+def _detect_linear_batch(y_d, psi_d, cons, theta, varn, n_tx, kind, es, labels, x_d_true, noise,
+                         maxlog, want, return_device, prior_llr):
     torch = _torch()
     es = _linear_es(torch, cons, es)                   # from the caller's table, before the upload
     Yd, Ps, Cs, Th, Xd = (_cdev(torch, x) for x in (y_d, psi_d, cons, theta, x_d_true))
-    lab = _detect_labels(Cs.shape[0], labels, "llr" in want or Xd is not None)
+    lab = _detect_labels(Cs.shape[0], labels,
+                         "llr" in want or Xd is not None or prior_llr is not None)
     lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
     s2, s2t = _sigma2_arg(torch, varn, Yd.shape[0], noise)
+    la, _ = _prior_arg(torch, prior_llr, lab_d, Yd.shape[0], Yd.shape[1], int(n_tx), Cs.shape[0],
+                       kind[0] if isinstance(kind, tuple) else kind)
     out = _detect_linear_call(torch, Yd, Ps, Cs, Th, int(n_tx), kind, s2, s2t, es, lab_d, Xd,
-                              maxlog, tuple(want))
+                              maxlog, tuple(want), la=la)
     return _result(torch, out, return_device)
 
 
 def detect_linear(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, kind="mmse", es=None,
                   labels=None, X_d=None, noise="em", maxlog=False, want=_WANT_LINEAR,
-                  ep_passes=None):
+                  ep_passes=None, prior_llr=None):
     """detect_linear_batch for one trial in the reference's list layouts (as detect()).
     all_possibleSymbols may also be the (M,) table itself (the M^n_tx hypothesis table is never
     enumerated here and is out of reach at n_tx = 8); n_tx then follows from theta's length.
     ep_passes: the pass count of kind 'ep' (None: 5), as kind=('ep', ep_passes).
+    prior_llr (T_d,n_tx,log2 M): a-priori bit L-values, as detect_linear_prior_batch.
     Returns the dict of detect_linear_batch without the batch axis."""
     aps = np.asarray(all_possibleSymbols)
     T_d = len(Y_d)
@@ -1020,9 +1109,11 @@ def detect_linear(Y_d, PsiTilde_td, all_possibleSymbols, M, varn, theta, kind="m
         n_tx = aps.shape[1]
         cons = cons_from_aps(aps, int(M))
     xt = None if X_d is None else np.stack([np.asarray(x).reshape(-1) for x in X_d[:T_d]])[None]
-    r = detect_linear_batch(y, psi, cons, np.asarray(theta, dtype=complex).reshape(1, -1), varn,
-                            n_tx, kind=kind if ep_passes is None else (kind, ep_passes), es=es,
-                            labels=labels, x_d_true=xt, noise=noise, maxlog=maxlog, want=want)
+    r = detect_linear_prior_batch(y, psi, cons, np.asarray(theta, dtype=complex).reshape(1, -1),
+                                  varn, n_tx,
+                                  None if prior_llr is None else np.asarray(prior_llr)[None],
+                                  kind=kind if ep_passes is None else (kind, ep_passes), es=es,
+                                  labels=labels, x_d_true=xt, noise=noise, maxlog=maxlog, want=want)
     return {k: v[0] for k, v in r.items()}
 
 
@@ -1049,13 +1140,14 @@ def em_zero_init(Y_d, Y_p, T_d, T_p, Z_p, PsiTilde_td, all_possibleSymbols, M, v
 
 # ------------------------------------------------------------------ diagnostic stages
 def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0, varx=1.0,
-                workspace=True, return_status=False, ep_passes=None):
+                workspace=True, return_status=False, ep_passes=None, prior_llr=None, labels=None):
     """One device E-step (sbce_estep): returns m (B,T_d,n_tx), S (B,T_d,n_tx,n_tx) and, with
     return_status, the (B,) status words (SBCE_STATUS_DETECTOR: a ZF / MMSE decision past the
     hypothesis table, or a failed pivot of a symbol in "mmse_soft" / "zf_soft" / "ep").  mode: any of
     em_batch's ("ep" with ``ep_passes``).  varn may be one value or one per trial ((B,), as em_batch takes it).
     workspace=False passes no workspace (the exact sweep then prepares each symbol in
-    its own kernel instead of the separate preparation pass)."""
+    its own kernel instead of the separate preparation pass).  prior_llr / labels (mode "ep"):
+    a-priori bit L-values as em_batch (sbce_estep_prior)."""
     torch = _torch()
     lib = _lib.load()
     B, T_d, n_rx = np.shape(y_d)
@@ -1067,8 +1159,13 @@ def estep_batch(y_d, psi_d, cons, theta, varn, n_tx, mode="soft", partition_r=0,
                  check="theta" if np.ndim(varn) else None, workspace=workspace)
     mom = torch.zeros((B, T_d, n_tx + n_tx * n_tx), dtype=torch.complex128, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
-    _lib.check(lib.sbce_estep(st.dims, st.ptrs(), _MODES[mode], mom.data_ptr(), stream),
-               "sbce_estep")
+    pr = _Prior(*_prior_arg(torch, prior_llr, labels, B, T_d, n_tx, st.M, mode))
+    if pr.opts is None:
+        _lib.check(lib.sbce_estep(st.dims, st.ptrs(), _MODES[mode], mom.data_ptr(), stream),
+                   "sbce_estep")
+    else:
+        _lib.check(lib.sbce_estep_prior(st.dims, st.ptrs(), _MODES[mode], pr.ref(), mom.data_ptr(),
+                                        stream), "sbce_estep_prior")
     torch.cuda.current_stream().synchronize()
     mom = mom.cpu().numpy()
     out = mom[..., :n_tx], mom[..., n_tx:].reshape(B, T_d, n_tx, n_tx)
@@ -1258,8 +1355,11 @@ class EMEngine:
     """
 
     def __init__(self, batch, varn, mode="soft", solve="chol", x_d_true=None, h_true=None,
-                 partition_r=0, varx=1.0, x_sup=None, streams=1, early_stop=False, ep_passes=None):
-        """ep_passes: the pass count of mode "ep" (None: 5).  early_stop=True: the reference's oracle early stop on the true channel (PM.py:110-112,
+                 partition_r=0, varx=1.0, x_sup=None, streams=1, early_stop=False, ep_passes=None,
+                 prior_llr=None, labels=None):
+        """ep_passes: the pass count of mode "ep" (None: 5).  prior_llr (B,T_d,n_tx,log2 M) with
+        ``labels`` (None: Gray): a-priori bit L-values of the data symbols (mode "ep", one stream);
+        run(), capture(), estep() and detect_linear(kind="ep") then use them.  early_stop=True: the reference's oracle early stop on the true channel (PM.py:110-112,
         all_detectorsvsTd.py's five EMs) with h_true (or batch["h"]); ``iters_done`` then holds
         the iterations each trial of the last run() performed."""
         torch = _torch()
@@ -1298,6 +1398,9 @@ class EMEngine:
         self.mom =torch.zeros((B, T_d, self.n_tx + self.n_tx ** 2), dtype=torch.complex128,
                                device="cuda")
         self.x_sup = _cdev(torch, x_sup)
+        self.prior = _Prior(*_prior_arg(torch, prior_llr, labels, B, T_d, self.n_tx, self.M, mode))
+        if self.prior.opts is not None and int(streams) > 1:
+            raise ValueError("prior_llr runs on one stream (sbce_em_multi takes no prior)")
         if early_stop and self.h is None:
             raise ValueError("early_stop needs the true channel (h_true or batch['h'])")
         self.early_stop = bool(early_stop)
@@ -1330,6 +1433,11 @@ class EMEngine:
         cur = self.torch.cuda.current_stream() if stream is None else stream
         with self.torch.cuda.stream(cur):
             self.theta.copy_(self.theta0)
+        if not self.subs and self.prior.opts is not None:
+            rc = self.lib.sbce_em_prior(self.dims, self.ptrs, int(itera), self.mode, self.solve,
+                                        self.prior.ref(), None, None, cur.cuda_stream)
+            _lib.check(rc, "sbce_em_prior")
+            return self.theta
         if not self.subs:
             rc = self.lib.sbce_em(self.dims, self.ptrs, int(itera), self.mode, self.solve,
                                   cur.cuda_stream)
@@ -1366,8 +1474,9 @@ class EMEngine:
 
     def estep(self):
         """One E-step launch over the batch from the current theta (for kernel timing)."""
-        rc = self.lib.sbce_estep(self.dims, self.ptrs, self.mode, self.mom.data_ptr(),
-                                 self.torch.cuda.current_stream().cuda_stream)
+        rc = self.lib.sbce_estep_prior(self.dims, self.ptrs, self.mode, self.prior.ref(),
+                                       self.mom.data_ptr(),
+                                       self.torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "sbce_estep")
 
     def mstep(self):
@@ -1411,15 +1520,22 @@ class EMEngine:
                       maxlog=False, want=_WANT_LINEAR, return_device=False, ep_passes=None):
         """One sbce_detect_linear on the engine's resident y_d, psi_d, cons and CURRENT theta, on
         the current stream: the outputs of detect_linear_batch (n_tx up to 8).  x_d_true defaults
-        to the engine's own."""
+        to the engine's own.  An engine made with prior_llr passes it on to kind 'ep' (with the
+        engine's labelling; ``labels`` must then be left out)."""
         torch = self.torch
         xd = self.x_d if x_d_true is None else _cdev(torch, x_d_true)
-        lab = _detect_labels(self.M, labels, "llr" in want or xd is not None)
-        lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
+        la = None
+        if self.prior.opts is not None and (kind[0] if isinstance(kind, tuple) else kind) == "ep":
+            if labels is not None:
+                raise ValueError("the engine's prior_llr come with the engine's labels")
+            la, lab_d = self.prior.la, self.prior.lab
+        else:
+            lab = _detect_labels(self.M, labels, "llr" in want or xd is not None)
+            lab_d = torch.from_numpy(lab).to("cuda") if lab is not None else None
         s2, s2t = _sigma2_arg(torch, (self.varn, self.varn_t), self.B, noise)
         out = _detect_linear_call(torch, self.y_d, self.psi_d, self.cons, self.theta, self.n_tx,
                                   kind, s2, s2t, self.es_table if es is None else float(es), lab_d,
-                                  xd, maxlog, tuple(want), ep_passes)
+                                  xd, maxlog, tuple(want), ep_passes, la=la)
         return _result(torch, out, return_device)
 
     def nmse(self):

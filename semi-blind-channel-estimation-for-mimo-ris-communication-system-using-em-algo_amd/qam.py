@@ -43,6 +43,49 @@ def bits_of(labels):
     return ((labels[:, None] >> np.arange(m)[None, :]) & 1).astype(np.int8)
 
 
+def prior_llr_known(x, cons, labels):
+    """A-priori bit L-values log(P(bit = 0) / P(bit = 1)) that mark the symbols ``x`` (any shape,
+    each the table point nearest to it) as known: +inf where the symbol's bit is 0, -inf where it
+    is 1; shape x.shape + (log2 M,).  The library clamps them to +-64 (include/sbce.h)."""
+    cons = np.asarray(cons, dtype=complex).reshape(-1)
+    x = np.asarray(x, dtype=complex)
+    idx = np.argmin(np.abs(x[..., None] - cons), axis=-1)
+    return np.where(bits_of(labels)[idx] == 0, np.inf, -np.inf)
+
+
+_J_H1, _J_H2, _J_H3 = 0.3073, 0.8935, 1.1064
+
+
+def _j_inverse(i_a):
+    """sigma with J(sigma) = i_a for J(sigma) ~ (1 - 2^(-H1 sigma^(2 H2)))^H3, the usual closed
+    form of the consistent-Gaussian L-value's mutual information (2 H2 = 1.787)."""
+    return (-np.log2(1.0 - i_a ** (1.0 / _J_H3)) / _J_H1) ** (1.0 / (2.0 * _J_H2))
+
+
+def prior_llr_gaussian(bits, i_a, rng):
+    """The consistent-Gaussian a-priori model of EXIT analysis: La = (1 - 2 b) sigma^2 / 2 +
+    sigma n with n ~ N(0, 1) from ``rng`` (a numpy Generator or RandomState) and sigma =
+    J^-1(i_a), for the 0/1 array ``bits``.  i_a = 0 gives all zeros, i_a = 1 gives +-inf."""
+    bits = np.asarray(bits)
+    i_a = float(i_a)
+    if not 0.0 <= i_a <= 1.0:
+        raise ValueError("i_a must lie in [0, 1]")
+    sign = 1.0 - 2.0 * bits
+    if i_a == 0.0:
+        return np.zeros(bits.shape)
+    if i_a == 1.0:
+        return np.where(bits == 0, np.inf, -np.inf)
+    sigma = _j_inverse(i_a)
+    return sign * (sigma * sigma / 2.0) + sigma * rng.standard_normal(bits.shape)
+
+
+def bit_mutual_information(llr, bits):
+    """1 - mean log2(1 + e^{-(1 - 2 b) L}): the mutual information between the bits and their
+    L-values log(P(bit = 0) / P(bit = 1)), by the time average."""
+    z = -(1.0 - 2.0 * np.asarray(bits)) * np.asarray(llr, dtype=float)
+    return float(1.0 - np.mean(np.logaddexp(0.0, z)) / np.log(2.0))
+
+
 def all_possible_symbols(cons, n_tx):
     """J = M^n_tx hypotheses in itertools.product order (first stream slowest)."""
     cons = np.asarray(cons)
