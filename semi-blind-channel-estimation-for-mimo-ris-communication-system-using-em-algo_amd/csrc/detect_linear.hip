@@ -6,8 +6,9 @@
 //   ZF    x_soft_a = z_a,      nu_a = sigma2 g_a
 // and each stream is demapped on its own: d_s = |x_soft_a - cons[s]|^2, weights e^{-d_s / nu_a}.
 //
-// Work split (staging, solve and estimate are linear_solve.h's, shared with the soft ZF / MMSE
-// E-step of estep_linear.hip).  One workgroup of 4 waves takes 32 consecutive symbols of ONE trial.
+// Work split (the lane split, staging, solve, estimate and moment store are linear_solve.h's,
+// shared with the E-steps of estep_linear.hip).  One workgroup of 4 waves takes 32 consecutive
+// symbols of ONE trial.
 //   staging  theta of the trial goes through LDS in tiles of 32 rows of P (32 x 64 x 16 B = 32 KB)
 //            beside the tile's 32 x 32 phases of psi_d (16 KB), both by coalesced 16-byte loads.
 //            Wave w forms H of its 8 symbols: lane = (entry e of the NE = NT NR, symbol subset g);
@@ -34,49 +35,89 @@
 //
 // SBCE_LINEAR_EP (the EP instantiation of the kernel): the solve and the estimate are replaced by
 // the passes of ep_solve.h on the same staged H, and x_soft = t, nu = h2 are the cavity mean and
-// variance of the last pass; everything after them is the same code.  The MMSE / ZF instantiation
-// keeps its statements in their former order and LinearArgs its former offsets (the new field is
-// last): its instructions are those of the kernel before the EP flag.
+// variance of the last pass; everything after them is the same code.
 #include "ep_prior.h"
 
 namespace sbce {
 
 namespace {
 
+// The LDS of a detection kernel
+struct DetectLinearLds {
+    cd buf[kLinBuf];
+    cd cons[64];
+    int lab[64];
+    int cnt[3];        // symbol errors, bit errors, failed-pivot flag
+};
+
+// The head of both detection kernels: the table and the labels (the identity by default) to LDS,
+// the counters to 0, H_t of the workgroup's symbols staged.  Out: the lane's work.
+template <int NT>
+__device__ __forceinline__ LinSplit detect_linear_head(const LinearArgs& a, DetectLinearLds& lds) {
+    const LinSplit sp = lin_split(NT, a.Td, a.chunks);
+    const int NE = NT * a.NR;
+    lin_load_table(lds.cons, lds.lab, a.cons, a.labels, a.M);
+    if (threadIdx.x < 3) lds.cnt[threadIdx.x] = 0;
+    lin_stage_h(lds.buf, a.theta + (size_t)sp.b * a.P * NE, a.psid + sp.bt * a.P, NE, a.P, sp.t0,
+                sp.tend);
+    return sp;
+}
+
+// The tail of both detection kernels, after the demapper and its post and llr stores: the stream's
+// estimate and decision, the error counts against x_d_true (nearest table point, ties to the
+// lowest s), the failed-pivot flag, the moments, and the workgroup's adds to err and status.
+template <int NT>
+__device__ __forceinline__ void detect_linear_tail(const LinearArgs& a, DetectLinearLds& lds,
+                                                   const LinSplit& sp, cd xs, double nu, int idx,
+                                                   bool fail, cd mean, double saa) {
+    const size_t o = sp.sym * NT + sp.aa;
+    if (sp.act) {
+        if (a.xsoft) a.xsoft[o] = xs;
+        if (a.nu) a.nu[o] = nu;
+        if (a.xhat) a.xhat[o] = lds.cons[idx];
+        if (a.idx) a.idx[o] = idx;
+        if (a.err) {
+            const cd xt = a.xd[o];
+            double bd = INFINITY;
+            int bi = 0;
+            for (int s = 0; s < a.M; ++s) {
+                const double dx = cabs2(csub(lds.cons[s], xt));
+                if (dx < bd) {
+                    bd = dx;
+                    bi = s;
+                }
+            }
+            if (bi != idx) {
+                atomicAdd(&lds.cnt[0], 1);
+                atomicAdd(&lds.cnt[1], __popc((unsigned)(lds.lab[bi] ^ lds.lab[idx])));
+            }
+        }
+        if (fail) lds.cnt[2] = 1;
+    }
+    if (a.mom) lin_store_moments<NT>(a.mom, sp, mean, saa);   // uniform: every lane calls it
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (a.err && (lds.cnt[0] | lds.cnt[1])) {
+            atomicAdd(&a.err[2 * sp.b], lds.cnt[0]);
+            atomicAdd(&a.err[2 * sp.b + 1], lds.cnt[1]);
+        }
+        if (a.status && lds.cnt[2]) atomicOr(&a.status[sp.b], SBCE_STATUS_NONHPD);
+    }
+}
+
 template <int NT, bool EP>
 __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a) {
-    __shared__ cd buf_s[kLinBuf];
-    __shared__ cd cons_s[64];
-    __shared__ int lab_s[64];
-    __shared__ int cnt_s[3];        // symbol errors, bit errors, failed-pivot flag
+    __shared__ DetectLinearLds lds;
+    const LinSplit sp = detect_linear_head<NT>(a, lds);
+    const cd* cons_s = lds.cons;
+    const int* lab_s = lds.lab;
+    const int NR = a.NR, M = a.M, lgM = a.lgM;
+    const int aa = sp.aa, lane = sp.lane;
+    const size_t sym = sp.sym;
 
-    const int NR = a.NR, P = a.P, Td = a.Td, M = a.M, lgM = a.lgM;
-    const int NE = NT * NR;
-    const int b = blockIdx.x / a.chunks, ch = blockIdx.x % a.chunks;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int t0 = ch * kLinSym;
-    const int tend = t0 + kLinSym < Td ? t0 + kLinSym : Td;
-    const size_t bt = (size_t)b * Td;
-
-    if (tid < M) {
-        cons_s[tid] = a.cons[tid];
-        lab_s[tid] = a.labels ? a.labels[tid] : tid;
-    }
-    if (tid < 3) cnt_s[tid] = 0;
-
-    // ---- staging: H_t of the workgroup's symbols
-    lin_stage_h(buf_s, a.theta + (size_t)b * P * NE, a.psid + bt * P, NE, P, t0, tend);
-
-    // ---- solve: 8 lanes per symbol, lane a = column a.  Lanes past NT and groups past the chunk
-    // repeat a valid column (no divergence around the cross-lane moves) and store nothing.
-    const int grp = lane >> 3, al = lane & 7;
-    const int ts = t0 + w * 8 + grp;
-    const bool act = al < NT && ts < tend;
-    const int aa = al < NT ? al : 0;
-    const int k = ts < tend ? w * 8 + grp : tend - 1 - t0;
-    const size_t sym = bt + t0 + k;
-    const cd* Hs = buf_s + k * kLinHS;
-    const double s2 = a.sigma2_t ? a.sigma2_t[b] : a.sigma2;
+    // ---- solve: 8 lanes per symbol, lane a = column a
+    const cd* Hs = lds.buf + sp.k * kLinHS;
+    const double s2 = a.sigma2_t ? a.sigma2_t[sp.b] : a.sigma2;
     const bool mmse = a.kind == SBCE_LINEAR_MMSE;
     const double rho = mmse ? s2 / a.es : 0.0;
 
@@ -142,12 +183,8 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
     mean = cmk(mean.x / Z, mean.y / Z);
     saa /= Z;
 
-    const size_t o = sym * NT + aa;
-    if (act) {
-        if (a.xsoft) a.xsoft[o] = xs;
-        if (a.nu) a.nu[o] = nu;
-        if (a.xhat) a.xhat[o] = cons_s[idx];
-        if (a.idx) a.idx[o] = idx;
+    if (sp.act) {
+        const size_t o = sym * NT + aa;
         if (a.post)
             for (int s = 0; s < M; ++s) {
                 const double d = cabs2(csub(xs, cons_s[s]));
@@ -162,47 +199,13 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
                     a.llr[o * lgM + i] = l;
                 }
         }
-        if (a.err) {
-            const cd xt = a.xd[o];
-            double bd = INFINITY;
-            int bi = 0;
-            for (int s = 0; s < M; ++s) {
-                const double dx = cabs2(csub(cons_s[s], xt));
-                if (dx < bd) {
-                    bd = dx;
-                    bi = s;
-                }
-            }
-            if (bi != idx) {
-                atomicAdd(&cnt_s[0], 1);
-                atomicAdd(&cnt_s[1], __popc((unsigned)(lab_s[bi] ^ lab_s[idx])));
-            }
-        }
-        if (fail) cnt_s[2] = 1;
     }
-    if (a.mom) {                     // uniform: the cross-lane moves see every lane
-        cd* mo = a.mom + sym * (NT + NT * NT);
-        if (act) mo[aa] = mean;
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const cd mq = bperm_c(mean, ((lane & 56) | q) << 2);
-            if (act) mo[NT + aa * NT + q] = q == aa ? cmk(saa, 0.0) : cmulc(mean, mq);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (a.err && (cnt_s[0] | cnt_s[1])) {
-            atomicAdd(&a.err[2 * b], cnt_s[0]);
-            atomicAdd(&a.err[2 * b + 1], cnt_s[1]);
-        }
-        if (a.status && cnt_s[2]) atomicOr(&a.status[b], SBCE_STATUS_NONHPD);
-    }
+    detect_linear_tail<NT>(a, lds, sp, xs, nu, idx, fail, mean, saa);
 }
 
 // sbce_detect_linear_prior: the EP instantiation above with a-priori bit L-values
 // la [B][Td][NT][lgM] -- the passes start from the prior's moments and every demapper weight
-// carries the point's a-priori probability (ep_prior.h).  A kernel of its own, so that the
-// instantiations above keep their instructions.  x_soft = t and nu = h2 are the extrinsic
+// carries the point's a-priori probability (ep_prior.h).  x_soft = t and nu = h2 are the extrinsic
 // estimate of the last pass; post, the moments and the decision are a-posteriori (exponent
 // -d_s / h2 + lp[s], the decision its argmax with ties to the lowest s); llr = L_post - La is
 // extrinsic.  A dead stream (failed symbol, or mu <= 0) has x_soft = 0, nu = +inf, post = the
@@ -210,34 +213,14 @@ __global__ __launch_bounds__(kLinThreads) void detect_linear_kernel(LinearArgs a
 template <int NT>
 __global__ __launch_bounds__(kLinThreads, 3) void detect_linear_prior_kernel(LinearArgs a,
                                                                              const double* la) {
-    __shared__ cd buf_s[kLinBuf];
-    __shared__ cd cons_s[64];
-    __shared__ int lab_s[64];
-    __shared__ int cnt_s[3];        // symbol errors, bit errors, failed-pivot flag
-
-    const int NR = a.NR, P = a.P, Td = a.Td, M = a.M, lgM = a.lgM;
-    const int NE = NT * NR;
-    const int b = blockIdx.x / a.chunks, ch = blockIdx.x % a.chunks;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int t0 = ch * kLinSym;
-    const int tend = t0 + kLinSym < Td ? t0 + kLinSym : Td;
-    const size_t bt = (size_t)b * Td;
-
-    if (tid < M) {
-        cons_s[tid] = a.cons[tid];
-        lab_s[tid] = a.labels[tid];
-    }
-    if (tid < 3) cnt_s[tid] = 0;
-
-    lin_stage_h(buf_s, a.theta + (size_t)b * P * NE, a.psid + bt * P, NE, P, t0, tend);
-
-    const int grp = lane >> 3, al = lane & 7;
-    const int ts = t0 + w * 8 + grp;
-    const bool act = al < NT && ts < tend;
-    const int aa = al < NT ? al : 0;
-    const int k = ts < tend ? w * 8 + grp : tend - 1 - t0;
-    const size_t sym = bt + t0 + k;
-    const double s2 = a.sigma2_t ? a.sigma2_t[b] : a.sigma2;
+    __shared__ DetectLinearLds lds;
+    const LinSplit sp = detect_linear_head<NT>(a, lds);
+    const cd* cons_s = lds.cons;
+    const int* lab_s = lds.lab;
+    const int NR = a.NR, M = a.M, lgM = a.lgM;
+    const int aa = sp.aa, lane = sp.lane;
+    const size_t sym = sp.sym;
+    const double s2 = a.sigma2_t ? a.sigma2_t[sp.b] : a.sigma2;
     const size_t o = sym * NT + aa;
 
     const EpPrior pr = ep_prior_load(la + o * lgM, lgM);
@@ -246,7 +229,7 @@ __global__ __launch_bounds__(kLinThreads, 3) void detect_linear_prior_kernel(Lin
     bool dead, fail;
     {
         cd c0[NT + 1];
-        ep_gram<NT>(buf_s + k * kLinHS, a.yd + sym * NR, NR, aa, c0);
+        ep_gram<NT>(lds.buf + sp.k * kLinHS, a.yd + sym * NR, NR, aa, c0);
         ep_prior_run<NT>(c0, cons_s, lab_s, M, lgM, pr, s2, a.es, a.passes, aa, lane, xs, nu, inv,
                          dead, fail);
     }
@@ -300,11 +283,7 @@ __global__ __launch_bounds__(kLinThreads, 3) void detect_linear_prior_kernel(Lin
     mean = cmk(mean.x / Z, mean.y / Z);
     saa /= Z;
 
-    if (act) {
-        if (a.xsoft) a.xsoft[o] = xs;
-        if (a.nu) a.nu[o] = nu;
-        if (a.xhat) a.xhat[o] = cons_s[idx];
-        if (a.idx) a.idx[o] = idx;
+    if (sp.act) {
         if (a.post)
             for (int s = 0; s < M; ++s)
                 a.post[o * M + s] =
@@ -318,41 +297,8 @@ __global__ __launch_bounds__(kLinThreads, 3) void detect_linear_prior_kernel(Lin
                     a.llr[o * lgM + i] = dead ? 0.0 : l - ep_prior_la(pr, i);
                 }
         }
-        if (a.err) {
-            const cd xt = a.xd[o];
-            double bd = INFINITY;
-            int bi = 0;
-            for (int s = 0; s < M; ++s) {
-                const double dx = cabs2(csub(cons_s[s], xt));
-                if (dx < bd) {
-                    bd = dx;
-                    bi = s;
-                }
-            }
-            if (bi != idx) {
-                atomicAdd(&cnt_s[0], 1);
-                atomicAdd(&cnt_s[1], __popc((unsigned)(lab_s[bi] ^ lab_s[idx])));
-            }
-        }
-        if (fail) cnt_s[2] = 1;
     }
-    if (a.mom) {                     // uniform: the cross-lane moves see every lane
-        cd* mo = a.mom + sym * (NT + NT * NT);
-        if (act) mo[aa] = mean;
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const cd mq = bperm_c(mean, ((lane & 56) | q) << 2);
-            if (act) mo[NT + aa * NT + q] = q == aa ? cmk(saa, 0.0) : cmulc(mean, mq);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (a.err && (cnt_s[0] | cnt_s[1])) {
-            atomicAdd(&a.err[2 * b], cnt_s[0]);
-            atomicAdd(&a.err[2 * b + 1], cnt_s[1]);
-        }
-        if (a.status && cnt_s[2]) atomicOr(&a.status[b], SBCE_STATUS_NONHPD);
-    }
+    detect_linear_tail<NT>(a, lds, sp, xs, nu, idx, fail, mean, saa);
 }
 
 // err[b][0..1] = 0 and status[b] = 0 (each when set) ahead of the detection kernel's integer adds
@@ -363,20 +309,6 @@ __global__ __launch_bounds__(256) void linear_zero_kernel(int32_t* err, int32_t*
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (err && i < 2 * B) err[i] = 0;
     if (status && i < B) status[i] = 0;
-}
-
-template <int NT>
-hipError_t launch_nt(const LinearArgs& a, const double* la, hipStream_t s) {
-    if (la)
-        hipLaunchKernelGGL(detect_linear_prior_kernel<NT>, dim3((unsigned)(a.B * a.chunks)),
-                           dim3(kLinThreads), 0, s, a, la);
-    else if (a.kind == SBCE_LINEAR_EP)
-        hipLaunchKernelGGL((detect_linear_kernel<NT, true>), dim3((unsigned)(a.B * a.chunks)),
-                           dim3(kLinThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL((detect_linear_kernel<NT, false>), dim3((unsigned)(a.B * a.chunks)),
-                           dim3(kLinThreads), 0, s, a);
-    return hipGetLastError();
 }
 
 }  // namespace
@@ -399,17 +331,17 @@ hipError_t launch_detect_linear_prior(LinearArgs a, const double* la, hipStream_
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    switch (a.NT) {
-        case 1: return launch_nt<1>(a, la, s);
-        case 2: return launch_nt<2>(a, la, s);
-        case 3: return launch_nt<3>(a, la, s);
-        case 4: return launch_nt<4>(a, la, s);
-        case 5: return launch_nt<5>(a, la, s);
-        case 6: return launch_nt<6>(a, la, s);
-        case 7: return launch_nt<7>(a, la, s);
-        case 8: return launch_nt<8>(a, la, s);
-    }
-    return hipErrorInvalidValue;
+    return lin_dispatch_nt(a.NT, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        const dim3 grid((unsigned)(a.B * a.chunks)), block(kLinThreads);
+        if (la)
+            hipLaunchKernelGGL(detect_linear_prior_kernel<NT>, grid, block, 0, s, a, la);
+        else if (a.kind == SBCE_LINEAR_EP)
+            hipLaunchKernelGGL((detect_linear_kernel<NT, true>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((detect_linear_kernel<NT, false>), grid, block, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace sbce

@@ -1,9 +1,9 @@
 // Device code of soft-input expectation propagation (include/sbce.h sbce_detect_linear_prior,
-// sbce_estep_prior), shared by estep_ep_prior.hip and the prior kernel of
-// detect_linear.hip.  The passes are ep_solve.h's -- the solve, the pivot rule and the cavity are
-// ep_solve and ep_cavity themselves -- with two changes: the state starts from the moments of the
-// a-priori pmf instead of the uniform one, and the demapper weighs every table point by its
-// a-priori probability.
+// sbce_estep_prior), shared by the prior kind of estep_linear.hip and the prior
+// kernel of detect_linear.hip.  The passes are ep_solve.h's -- the solve, the pivot rule, the
+// cavity and the pass loop are ep_solve, ep_cavity and ep_passes themselves -- with two changes:
+// the state starts from the moments of the a-priori pmf instead of the uniform one, and the
+// demapper weighs every table point by its a-priori probability.
 // The prior of stream a is given as lgM bit L-values La_i = log(P(bit_i = 0) / P(bit_i = 1)),
 // sanitised on load (NaN -> 0, clamped to +-kPriorClamp), with bit_i(s) = (labels[s] >> i) & 1:
 //   lp[s] = -sum_i bit_i(s) La_i - max_s(...)  =  -sum_i |La_i| [bit_i(s) != (La_i < 0)]
@@ -66,7 +66,7 @@ __device__ __forceinline__ double ep_prior_exponent(const EpPrior& p, cd cs, int
     return fma(-cabs2(csub(t, cs)), inv, ep_prior_lp(p, lab, lgM));
 }
 
-// ep_demap with the prior: weights e^{exponent - largest exponent}, posterior mean and second
+// lin_demap with the prior: weights e^{exponent - largest exponent}, posterior mean and second
 // moment.  inv = 0 (a dead stream, or the call that forms the prior's own moments) leaves the
 // a-priori pmf.
 __device__ __forceinline__ void ep_prior_demap(const cd* cons_s, const int* lab_s, int M, int lgM,
@@ -90,37 +90,22 @@ __device__ __forceinline__ void ep_prior_demap(const cd* cons_s, const int* lab_
 }
 
 // ep_run from the prior's moments: r = s2 / v0, q = s2 xbar / v0 with xbar and v0 the mean and the
-// floored variance of the a-priori pmf.  Out: the cavity (t, h2, inv) of the last pass, dead = this
-// stream is dead in it, fail = a pivot failed in some pass (the whole group agrees).
+// floored variance of the a-priori pmf, and ep_prior_demap between the passes.  Out: ep_passes'.
 template <int NT>
 __device__ __forceinline__ void ep_prior_run(const cd (&c0)[NT + 1], const cd* cons_s,
                                              const int* lab_s, int M, int lgM, const EpPrior& p,
                                              double s2, double es, int passes, int aa, int lane,
                                              cd& t, double& h2, double& inv, bool& dead, bool& fail) {
-    const double vfloor = kEpVarFloor * es;
     cd mean;
     double saa;
     ep_prior_demap(cons_s, lab_s, M, lgM, p, czero(), 0.0, mean, saa);
-    double r = s2 / fmax(saa - cabs2(mean), vfloor);
-    cd q = cscale(mean, r);
-    fail = false;
-    for (int l = 1;; ++l) {
-        double g;
-        cd z;
-        bool f;
-        ep_solve<NT>(c0, r, q, aa, lane, g, z, f);
-        fail = fail || f;
-        ep_cavity(r, q, s2, g, z, fail, t, h2, inv, dead);
-        if (l >= passes) break;
-        ep_prior_demap(cons_s, lab_s, M, lgM, p, t, inv, mean, saa);
-        const double v = fmax(saa - cabs2(mean), vfloor);
-        const double iv = 1.0 / v;
-        const double rn = s2 * (iv - inv);
-        const cd qn = cmk(s2 * (mean.x * iv - t.x * inv), s2 * (mean.y * iv - t.y * inv));
-        const bool up = !dead && rn > 0.0 && rn < INFINITY;
-        r = up ? kEpBeta * rn + (1.0 - kEpBeta) * r : r;
-        q = csel(up, cmk(kEpBeta * qn.x + (1.0 - kEpBeta) * q.x, kEpBeta * qn.y + (1.0 - kEpBeta) * q.y), q);
-    }
+    const double r = s2 / fmax(saa - cabs2(mean), kEpVarFloor * es);
+    ep_passes<NT>(
+        c0, r, cscale(mean, r), s2, es, passes, aa, lane,
+        [&](cd tc, double ic, cd& mc, double& sc) {
+            ep_prior_demap(cons_s, lab_s, M, lgM, p, tc, ic, mc, sc);
+        },
+        t, h2, inv, dead, fail);
 }
 
 }  // namespace sbce

@@ -1,5 +1,5 @@
 // Device code of expectation propagation (EP; Cespedes et al., IEEE Trans. Commun. 2014) shared by
-// the EP E-step (estep_ep.hip, SBCE_ESTEP_EP) and the EP kind of the linear soft detector
+// the EP E-steps (estep_linear.hip, SBCE_ESTEP_EP) and the EP kind of the linear soft detector
 // (detect_linear.hip, SBCE_LINEAR_EP); DESIGN.md §3.13.  EP loops the LMMSE solve of
 // linear_solve.h, each pass using the per-stream posterior means and variances of the pass before
 // as a Gaussian prior.  Per symbol, with G = H^H H, u = H^H y, s2 the posterior denominator and
@@ -9,7 +9,7 @@
 //   2. g_a = (A^-1)_aa,  z = A^-1 (u + q)
 //   3. mu_a = 1 - r_a g_a;  cavity variance h2_a = s2 g_a / mu_a;  cavity mean
 //      t_a = (z_a - g_a q_a) / mu_a
-//   4. demap on (t_a, h2_a): weights e^{-(|t_a - cons[s]|^2 - d_min) / h2_a},
+//   4. demap on (t_a, h2_a) (lin_demap): weights e^{-(|t_a - cons[s]|^2 - d_min) / h2_a},
 //      m_a = sum post cons,  s_a = sum post |cons|^2
 //   5. l = p: stop.  Else v_a = max(s_a - |m_a|^2, kEpVarFloor es),  r' = s2 (1 / v_a - 1 / h2_a),
 //      q' = s2 (m_a / v_a - t_a / h2_a);  r' finite and > 0: r_a <- beta r' + (1 - beta) r_a and
@@ -109,46 +109,28 @@ __device__ __forceinline__ void ep_cavity(double r, cd q, double s2, double g, c
     inv = dead ? 0.0 : 1.0 / h2;
 }
 
-// The soft demapper of both linear kernels on (t, 1 / h2): posterior mean and second moment.
-__device__ __forceinline__ void ep_demap(const cd* cons_s, int M, cd t, double inv, cd& mean,
-                                         double& saa) {
-    double dmin = INFINITY;
-    for (int s = 0; s < M; ++s) dmin = fmin(dmin, cabs2(csub(t, cons_s[s])));
-    double Z = 0.0;
-    saa = 0.0;
-    mean = czero();
-    for (int s = 0; s < M; ++s) {
-        const cd cs = cons_s[s];
-        const double e = fexp_neg(-(cabs2(csub(t, cs)) - dmin) * inv);
-        Z += e;
-        mean = caxpy(mean, e, cs);
-        saa = fma(e, cabs2(cs), saa);
-    }
-    mean = cmk(mean.x / Z, mean.y / Z);
-    saa /= Z;
-}
-
-// `passes` passes from G's column and conj(u) in c0.  Out: the cavity (t, h2, inv) of the last
-// pass and fail = a pivot failed in some pass (the whole group agrees; every stream is then dead).
-template <int NT>
-__device__ __forceinline__ void ep_run(const cd (&c0)[NT + 1], const cd* cons_s, int M, double s2,
-                                       double es, int passes, int aa, int lane, cd& t, double& h2,
-                                       double& inv, bool& fail) {
-    double r = s2 / es;
-    cd q = czero();
+// The pass loop from the state (r, q): solve, cavity, and between two passes the demapper's moments
+// and the damped update of step 5.  demap(t, inv, mean, saa) is the kind's demapper (the plain one,
+// or the one that carries the a-priori pmf).  Out: the cavity (t, h2, inv) of the last pass, dead =
+// this stream is dead in it, fail = a pivot failed in some pass (the whole group agrees; every
+// stream is then dead).
+template <int NT, class Demap>
+__device__ __forceinline__ void ep_passes(const cd (&c0)[NT + 1], double r, cd q, double s2,
+                                          double es, int passes, int aa, int lane, Demap demap,
+                                          cd& t, double& h2, double& inv, bool& dead, bool& fail) {
     const double vfloor = kEpVarFloor * es;
     fail = false;
     for (int l = 1;; ++l) {
         double g;
         cd z;
-        bool f, dead;
+        bool f;
         ep_solve<NT>(c0, r, q, aa, lane, g, z, f);
         fail = fail || f;
         ep_cavity(r, q, s2, g, z, fail, t, h2, inv, dead);
         if (l >= passes) break;
         cd mean;
         double saa;
-        ep_demap(cons_s, M, t, inv, mean, saa);
+        demap(t, inv, mean, saa);
         const double v = fmax(saa - cabs2(mean), vfloor);
         const double iv = 1.0 / v;
         const double rn = s2 * (iv - inv);
@@ -157,6 +139,19 @@ __device__ __forceinline__ void ep_run(const cd (&c0)[NT + 1], const cd* cons_s,
         r = up ? kEpBeta * rn + (1.0 - kEpBeta) * r : r;
         q = csel(up, cmk(kEpBeta * qn.x + (1.0 - kEpBeta) * q.x, kEpBeta * qn.y + (1.0 - kEpBeta) * q.y), q);
     }
+}
+
+// `passes` passes from the uniform pmf's state (r = s2 / es, q = 0) with the plain demapper
+// (lin_demap), on G's column and conj(u) in c0.
+template <int NT>
+__device__ __forceinline__ void ep_run(const cd (&c0)[NT + 1], const cd* cons_s, int M, double s2,
+                                       double es, int passes, int aa, int lane, cd& t, double& h2,
+                                       double& inv, bool& fail) {
+    bool dead;
+    ep_passes<NT>(
+        c0, s2 / es, czero(), s2, es, passes, aa, lane,
+        [&](cd tc, double ic, cd& mc, double& sc) { lin_demap(cons_s, M, tc, ic, mc, sc); }, t, h2,
+        inv, dead, fail);
 }
 
 }  // namespace sbce

@@ -1,6 +1,6 @@
 // E-step routing: which unit computes the per-symbol posterior moments of (pb, mode).
-//   soft ZF / MMSE                 estep_linear.hip
-//   expectation propagation        estep_ep.hip; with a-priori L-values estep_ep_prior.hip
+//   soft ZF / MMSE, expectation    estep_linear.hip (one kernel template over the kind; EP with
+//   propagation                    a-priori L-values when EstepArgs::la is set)
 //   PM / ZF / MMSE / Gauss         estep_pm.hip
 //   exact soft / hard              the MFMA sweep (estep_sweep.hip) where one exists for the shape
 //                                  (JA, JB >= 16), behind the preparation or the sphere pass
@@ -21,15 +21,14 @@ bool estep_supported(const Problem& pb, int mode) {
 // the enumeration, the n_tx = 4 factorised-weight pass and the MFMA sweep (listed or not) -- every
 // writer of a soft / hard E-step that takes the sweep branch below at n_tx >= 3.  Not the VALU
 // kernel, the n_tx = 2 factorised passes (estep_pair.hip), the PM / ZF / MMSE / Gauss kernels or
-// the soft ZF / MMSE and EP kernels (estep_linear.hip, estep_ep.hip).
+// the soft ZF / MMSE and EP kernels (estep_linear.hip).
 bool estep_momfold_supported(const Problem& pb, int mode) {
     if (mode != SBCE_ESTEP_SOFT && mode != SBCE_ESTEP_HARD) return false;
     return !g_debug.estep_valu && pb.NT >= 3 && estep_sweep_plan(pb).ok;
 }
 
 hipError_t launch_estep(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s) {
-    if (estep_linear_mode(mode)) return launch_estep_linear(pb, a, mode, s);
-    if (mode == SBCE_ESTEP_EP) return a.la ? launch_estep_ep_prior(pb, a, s) : launch_estep_ep(pb, a, s);
+    if (estep_linear_mode(mode) || mode == SBCE_ESTEP_EP) return launch_estep_linear(pb, a, mode, s);
     if (a.la) return hipErrorInvalidValue;   // the entry points accept a prior with EP only
     if (mode >= SBCE_ESTEP_PM && mode <= SBCE_ESTEP_GAUSS) return launch_estep_pm(pb, a, mode, pb.pr, s);
     const SweepPlan sp = estep_sweep_plan(pb);

@@ -1,9 +1,13 @@
-// Device code shared by the linear soft detector (detect_linear.hip) and the soft ZF / MMSE
-// E-step (estep_linear.hip): the staging of H_t for the 32 symbols of a workgroup, the per-symbol
-// Cholesky with its folded forward substitution, and the per-stream estimate.  The work split is
-// described in detect_linear.hip's header comment; both kernels run these steps operation for
-// operation, so their x_soft and nu are the same bits.
+// Device code shared by the linear kernel family -- the soft ZF / MMSE, EP and soft-input EP
+// E-steps (estep_linear.hip) and the linear soft detector (detect_linear.hip): the work split of a
+// workgroup over its 32 symbols, the table in LDS, the staging of H_t, the per-symbol Cholesky with
+// its folded forward substitution, the per-stream estimate, the plain soft demapper and the
+// product-form moment store; and the host-side dispatch on n_tx.  The work split is described in
+// detect_linear.hip's header comment; every kernel runs these steps operation for operation, so
+// x_soft and nu of the ZF / MMSE detector and E-step are the same bits.
 #pragma once
+
+#include <type_traits>
 
 #include "sbce_internal.h"
 
@@ -24,6 +28,52 @@ __device__ __forceinline__ double group8_max(double v) {
     v = fmax(v, dpp_d<0xB1>(v));
     v = fmax(v, dpp_d<0x4E>(v));
     return fmax(v, dpp_d<0x141>(v));
+}
+
+// The work of one lane: workgroup blockIdx.x takes the symbols t0 .. tend - 1 of trial b (chunk
+// blockIdx.x % chunks), a group of 8 lanes per symbol, lane aa = column aa of the symbol's matrix.
+// Lanes past NT and groups past the chunk repeat a valid column and a valid symbol (no divergence
+// around the cross-lane moves, no read outside the trial) and store nothing: act is false.
+struct LinSplit {
+    int b, t0, tend;
+    size_t bt;         // b * Td: the trial's first symbol
+    int lane, aa, k;   // lane of the wave, column, row of H_s
+    bool act;
+    size_t sym;        // bt + t0 + k
+};
+__device__ __forceinline__ LinSplit lin_split(int NT, int Td, int chunks) {
+    LinSplit sp;
+    sp.b = blockIdx.x / chunks;
+    sp.t0 = (blockIdx.x % chunks) * kLinSym;
+    sp.tend = sp.t0 + kLinSym < Td ? sp.t0 + kLinSym : Td;
+    sp.bt = (size_t)sp.b * Td;
+    const int tid = threadIdx.x, w = tid >> 6;
+    sp.lane = tid & 63;
+    const int grp = sp.lane >> 3, al = sp.lane & 7;
+    const int ts = sp.t0 + w * 8 + grp;
+    sp.act = al < NT && ts < sp.tend;
+    sp.aa = al < NT ? al : 0;
+    sp.k = ts < sp.tend ? w * 8 + grp : sp.tend - 1 - sp.t0;
+    sp.sym = sp.bt + sp.t0 + sp.k;
+    return sp;
+}
+
+// The table, and the labels where the kernel keeps them (lab_s null: it does not; labels null: the
+// identity), to LDS.  lin_stage_h's barriers publish them.
+__device__ __forceinline__ void lin_load_table(cd* cons_s, int* lab_s, const cd* cons,
+                                               const int32_t* labels, int M) {
+    const int tid = threadIdx.x;
+    if (tid < M) {
+        cons_s[tid] = cons[tid];
+        if (lab_s) lab_s[tid] = labels ? labels[tid] : tid;
+    }
+}
+
+// es = mean |cons|^2 from the table in LDS: one ascending-s sum, the same bits on every lane
+__device__ __forceinline__ double lin_table_energy(const cd* cons_s, int M) {
+    double es = 0.0;
+    for (int s = 0; s < M; ++s) es += cabs2(cons_s[s]);
+    return es / (double)M;
 }
 
 // Staging: H_t of the symbols t0 .. tend - 1 of one trial into buf_s[kLinBuf], row k = symbol
@@ -148,6 +198,58 @@ __device__ __forceinline__ void lin_estimate(bool mmse, double rho, double s2, d
         nu = INFINITY;
     }
     inv = dead ? 0.0 : 1.0 / nu;
+}
+
+// The soft demapper of stream a on (xs, inv = 1 / nu): one scan of the table for the minimum
+// distance, one for the min-shifted sums (the nearest point has weight 1: nothing is 0 / 0).  Out:
+// the posterior mean and second moment.
+__device__ __forceinline__ void lin_demap(const cd* cons_s, int M, cd xs, double inv, cd& mean,
+                                          double& saa) {
+    double dmin = INFINITY;
+    for (int s = 0; s < M; ++s) dmin = fmin(dmin, cabs2(csub(xs, cons_s[s])));
+    double Z = 0.0;
+    saa = 0.0;
+    mean = czero();
+    for (int s = 0; s < M; ++s) {
+        const cd cs = cons_s[s];
+        const double e = fexp_neg(-(cabs2(csub(xs, cs)) - dmin) * inv);
+        Z += e;
+        mean = caxpy(mean, e, cs);
+        saa = fma(e, cabs2(cs), saa);
+    }
+    mean = cmk(mean.x / Z, mean.y / Z);
+    saa /= Z;
+}
+
+// The symbol's moments in the product form, mom [B][Td][NT + NT*NT]: m_a = mean, S[a][a] = saa,
+// S[a][q] = m_a conj(m_q).  Every lane of the wave calls it (the cross-lane moves see every lane);
+// the active ones store.
+template <int NT>
+__device__ __forceinline__ void lin_store_moments(cd* mom, const LinSplit& sp, cd mean,
+                                                  double saa) {
+    cd* mo = mom + sp.sym * (NT + NT * NT);
+    if (sp.act) mo[sp.aa] = mean;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+        const cd mq = bperm_c(mean, ((sp.lane & 56) | q) << 2);
+        if (sp.act) mo[NT + sp.aa * NT + q] = q == sp.aa ? cmk(saa, 0.0) : cmulc(mean, mq);
+    }
+}
+
+// f(std::integral_constant<int, NT>{}) for NT = 1 .. 8: the launchers' dispatch on n_tx
+template <class F>
+hipError_t lin_dispatch_nt(int NT, F f) {
+    switch (NT) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace sbce

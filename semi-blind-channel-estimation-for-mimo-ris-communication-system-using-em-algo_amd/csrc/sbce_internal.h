@@ -322,7 +322,7 @@ struct EstepArgs {
     // kernel of which does not carry the fold: estep_momfold_supported)
     int32_t* mchg = nullptr;          // [B]
     // a-priori bit L-values of the data symbols (sbce_prior_opts; SBCE_ESTEP_EP only, both set or
-    // both null): launch_estep then takes estep_ep_prior.hip's kernel
+    // both null): launch_estep then takes estep_linear.hip's prior kind
     const double* la = nullptr;       // [B][Td][NT][log2 M]
     const int32_t* labels = nullptr;  // [M]
 };
@@ -559,12 +559,15 @@ hipError_t launch_estep_pm(const Problem& pb, const EstepArgs& a, int mode, int 
                            hipStream_t s);
 bool estep_pm_supported(const Problem& pb, int partition_r, int mode);
 bool estep_supported(const Problem& pb, int mode);
-// soft ZF / MMSE E-step (estep_linear.hip): SBCE_ESTEP_MMSE_SOFT, SBCE_ESTEP_ZF_SOFT
+// The E-steps of the linear family (estep_linear.hip).  Soft ZF / MMSE: SBCE_ESTEP_MMSE_SOFT,
+// SBCE_ESTEP_ZF_SOFT
 bool estep_linear_mode(int mode);
 bool estep_linear_supported(const Problem& pb, int mode);   // n_tx, n_rx 1..8, M a power of two <= 64
+// mode: a soft ZF / MMSE mode, or SBCE_ESTEP_EP (soft-input EP when EstepArgs::la and ::labels are
+// set), each within its *_supported limits
 hipError_t launch_estep_linear(const Problem& pb, const EstepArgs& a, int mode, hipStream_t s);
 
-// expectation-propagation E-step (estep_ep.hip): SBCE_ESTEP_EP, pb.pr = the pass count (0: default)
+// expectation propagation: SBCE_ESTEP_EP, pb.pr = the pass count (0: default)
 constexpr int kEpDefaultPasses = 5;
 constexpr int kEpMaxPasses = 16;
 // the pass count of a caller's word (dims.partition_r, or flags bits 8..15 of the linear detector):
@@ -574,9 +577,6 @@ inline int ep_passes_of(int word) {
     return word >= 1 && word <= kEpMaxPasses ? word : -1;
 }
 bool estep_ep_supported(const Problem& pb);   // the soft MMSE E-step's limits, pr in 0..16
-hipError_t launch_estep_ep(const Problem& pb, const EstepArgs& a, hipStream_t s);
-// soft-input EP E-step (estep_ep_prior.hip): EstepArgs::la and ::labels set, limits as above
-hipError_t launch_estep_ep_prior(const Problem& pb, const EstepArgs& a, hipStream_t s);
 int estep_prep_stride(const Problem& pb);   // doubles per symbol, 0 if no MFMA sweep
 // pilots_factored: launch_pilot_factor already ran for these u_p (ppsi, pS, pflag valid)
 hipError_t launch_mstep_build(const Problem& pb, const MstepArgs& a, hipStream_t s,

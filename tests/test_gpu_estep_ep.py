@@ -1,4 +1,4 @@
-"""GPU tier of expectation propagation (csrc/ep_solve.h, csrc/estep_ep.hip and the EP kind of
+"""GPU tier of expectation propagation (csrc/ep_solve.h, csrc/estep_linear.hip and the EP kind of
 csrc/detect_linear.hip; SBCE_ESTEP_EP, SBCE_LINEAR_EP): sbce_estep's moments and every
 sbce_detect_linear output against the NumPy restatement (tests/ep_oracle.py), one pass against the
 soft MMSE kernels, bitwise determinism, the EM chain through sbce_em / sbce_em_multi /

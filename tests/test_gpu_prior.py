@@ -1,4 +1,4 @@
-"""GPU tier of soft-input expectation propagation (csrc/ep_prior.h, csrc/estep_ep_prior.hip and
+"""GPU tier of soft-input expectation propagation (csrc/ep_prior.h, csrc/estep_linear.hip and
 the prior kernel of csrc/detect_linear.hip; sbce_detect_linear_prior, sbce_estep_prior,
 sbce_em_prior): every output against the NumPy restatement (tests/prior_oracle.py), the prior-free
 calls bit for bit, tiling and determinism, the degenerate symbols, the EM chain against the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the soft-input EP E-step (csrc/estep_ep_prior.hip, sbce_estep_prior) and the moments-only
+"""Time the soft-input EP E-step (csrc/estep_linear.hip, sbce_estep_prior) and the moments-only
 soft-input EP detector call (sbce_detect_linear_prior) with HIP events at estep_ep_bench.py's
 shape -- 8x8, P = 65, T_d = 256, 16-QAM, B = 1000 -- beside the prior-free EP arms (sbce_estep,
 sbce_detect_linear) on the same buffers in the same process, for every pass count of --passes.

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the expectation-propagation E-step (csrc/estep_ep.hip) and the moments-only EP detector
+"""Time the expectation-propagation E-step (csrc/estep_linear.hip) and the moments-only EP detector
 call with HIP events at 8x8, P = 65, T_d = 256, 16-QAM, B = 1000, beside the soft MMSE E-step and
 the moments-only MMSE detector call on the same buffers in the same process.  One arm per pass
 count of --passes for the E-step, the default pass count for the detector.  The arms alternate
