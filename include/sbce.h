@@ -751,6 +751,84 @@ int sbce_em_prior(const sbce_dims* d, const sbce_ptrs* p, int iters, int estep_m
                   const sbce_prior_opts* pr, const sbce_noise_opts* nz, const sbce_conv_opts* cv,
                   void* hip_stream);
 
+/* ---- Soft-in / soft-out channel decoder (an additive extension of ABI 7: no existing struct or
+ * entry point changes): exact log-MAP (BCJR) decoding of a batch of codewords of one binary code,
+ * the block that produces the a-priori L-values the section above consumes.  Every L-value here is
+ * L = log(P(bit = 0) / P(bit = 1)), the convention of llr and la above.
+ * Code: rate 1/n, feed-forward, non-systematic; n in {2, 3}; constraint length K in 3..7, so
+ * S = 2^(K-1) states.  The generators g_j are K-bit integers whose bit K-1 taps the current input;
+ * bit K-1 and bit 0 of every generator must be set and no bit above K-1 (gen[2] is ignored at
+ * n = 2).  State s = (u_{t-1}, ..., u_{t-K+1}) with u_{t-1} at bit K-2; register word
+ * w = (u_t << (K-1)) | s; output c_j = parity(w & g_j); next state s' = w >> 1; the start state is
+ * 0.  With SBCE_SISO_TERMINATED n_steps = n_info + K - 1, the K - 1 tail inputs are forced to 0
+ * and the end state is 0; without it n_steps = n_info and every end state is allowed.
+ * Known answer: g = (7, 5) octal, u = 1011, terminated: the codeword is 11 10 00 01 01 11.
+ * Inputs: lc [B][n_steps n] float64, coded bit k = t n + j; la_u [B][n_info] (may be NULL: 0);
+ * perm int32 [n_steps n] (may be NULL: the identity), a bijection of 0 .. n_steps n - 1 -- the
+ * caller's contract, not checked: coded bit k is read from lc[b][perm[k]] and its extrinsic value
+ * written to le_c[b][perm[k]], so the de-interleaver and the interleaver cost no launch.  Every
+ * L-value is sanitised on load as la above: NaN becomes 0, values outside +-64 are clamped.
+ * Recursion, with Lc and La the sanitised values:
+ *   gamma_t(s, u) = -sum_j c_j(s, u) Lc[t][j] - u La[t]; the branch u = 1 does not exist at tail
+ *   steps.  alpha_0(0) = 0, else -inf; alpha_{t+1}(s') = lse over the two branches into s';
+ *   beta_{n_steps} = 0 at every allowed end state, else -inf; beta_t(s) = lse over the branches
+ *   out of s; A_t(s, u) = alpha_t(s) + gamma_t(s, u) + beta_{t+1}(s').
+ * Outputs (each may be NULL, at least one is required):
+ *   lapp_u[b][t]   lse_{u = 0} A_t - lse_{u = 1} A_t, t < n_info: the a-posteriori L-value
+ *   u_hat[b][t]    int32 [lapp_u < 0]; a tie gives 0
+ *   le_c[b][k]     (lse_{c_j = 0} A_t - lse_{c_j = 1} A_t) - Lc[t][j]: the EXTRINSIC L-value of
+ *                  coded bit k = t n + j, tail steps included, at position perm[k]
+ *   err[b]         int32: bit errors of u_hat against u_true (integer adds; zeroed by the call)
+ * With SBCE_DETECT_MAXLOG every lse above is a max (max-log-MAP).
+ * Numerical rules: every lse is shifted by the maximum of its own members; -inf is an ordinary
+ * value and lse of nothing but -inf is -inf.  An output is +-inf exactly when one of its two
+ * classes is empty, which (the sanitised inputs being finite) is a property of (code, t,
+ * termination) alone: lapp_u is always finite (both inputs leave every reachable state and reach
+ * an allowed end), le_c is infinite where every surviving path agrees on the coded bit -- g =
+ * (7, 5), n_info = 1, terminated: step 1 is entered in states 0 and 2 only and g = 5 gives 0 on
+ * both branches, so le_c[3] = +inf.  No output is NaN for any bit pattern of the inputs.  The metric rows are normalised by a fixed rule (each
+ * stored row minus state 0's metric of the row it was formed from), which cancels in every output.
+ * Determinism: no floating-point atomic; every order of summation is fixed by (K, n, n_steps,
+ * flags); codeword b of a B-codeword call is bitwise the B = 1 call, whatever the workspace held. */
+#define SBCE_SISO_TERMINATED 2  /* sbce_siso_dims.flags bit 1 (bit 0 is SBCE_DETECT_MAXLOG) */
+
+typedef struct sbce_siso_dims {
+    int32_t batch;      /* B: codewords (>= 1) */
+    int32_t n_info;     /* information bits per codeword (>= 1) */
+    int32_t k;          /* constraint length K (3..7) */
+    int32_t n;          /* coded bits per step (2..3) */
+    int32_t gen[3];     /* generators g_0 .. g_{n-1} */
+    int32_t flags;      /* SBCE_DETECT_MAXLOG, SBCE_SISO_TERMINATED; every other bit 0 */
+} sbce_siso_dims;
+
+typedef struct sbce_siso_ptrs {
+    const double*  lc;       /* [B][n_steps n] */
+    const double*  la_u;     /* may be NULL: [B][n_info] */
+    const int32_t* perm;     /* may be NULL: [n_steps n] */
+    const int32_t* u_true;   /* may be NULL unless err is set: [B][n_info], 0 / 1 */
+    double*  lapp_u;         /* may be NULL: [B][n_info] */
+    int32_t* u_hat;          /* may be NULL: [B][n_info] */
+    double*  le_c;           /* may be NULL: [B][n_steps n] */
+    int32_t* err;            /* may be NULL (requires u_true): [B]; zeroed by the call */
+    void* workspace;         /* the alpha and beta rows of the call, 16-byte aligned */
+    size_t workspace_bytes;
+} sbce_siso_ptrs;
+
+/* Device workspace of the decoder for `d`: 512 n_steps bytes per group of 64 / S codewords.
+ * Errors as sbce_siso_decode's checks of d. */
+int sbce_siso_workspace_bytes(const sbce_siso_dims* d, size_t* bytes);
+
+/* One decode is one kernel launch on `hip_stream`, preceded by one small kernel that zeroes `err`
+ * when it is set; no allocation, no synchronisation; capturable in a HIP graph as a linear chain
+ * of kernel nodes.
+ * Decided before any HIP call, in this order -- SBCE_EINVAL: null d / p / lc, batch or n_info < 1,
+ * an unknown flag bit; SBCE_EUNSUPPORTED: k outside 3..7 or n outside 2..3; SBCE_EINVAL: a
+ * generator without bit K-1 or bit 0, or with a bit above K-1; SBCE_EUNSUPPORTED:
+ * n_steps > 16384; SBCE_EINVAL: err without u_true, no output requested, a null workspace, a
+ * misaligned pointer (8 bytes float64, 4 int32, 16 workspace); SBCE_EWORKSPACE: workspace_bytes
+ * too small. */
+int sbce_siso_decode(const sbce_siso_dims* d, const sbce_siso_ptrs* p, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ SBCE_STATUS_SINGULAR = 32
 SBCE_STATUS_NOISE = 64
 SBCE_STATUS_CONVERGED = 128
 SBCE_DETECT_MAXLOG = 1
+SBCE_SISO_TERMINATED = 2
 SBCE_LINEAR_MMSE = 0
 SBCE_LINEAR_ZF = 1
 SBCE_LINEAR_EP = 3
@@ -58,7 +59,8 @@ EXPORTED = ("sbce_abi_version", "sbce_strerror", "sbce_workspace_bytes",
             "sbce_em_conv",
             "sbce_detect_linear_workspace_bytes", "sbce_detect_linear",
             "sbce_crb_workspace_bytes", "sbce_crb",
-            "sbce_detect_linear_prior", "sbce_estep_prior", "sbce_em_prior")
+            "sbce_detect_linear_prior", "sbce_estep_prior", "sbce_em_prior",
+            "sbce_siso_workspace_bytes", "sbce_siso_decode")
 
 
 class SbceUnavailable(RuntimeError):
@@ -161,6 +163,19 @@ class CrbOpts(ctypes.Structure):
 class PriorOpts(ctypes.Structure):
     """sbce_prior_opts (include/sbce.h): a-priori bit L-values of sbce_estep_prior / sbce_em_prior."""
     _fields_ = [("la", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("flags", ctypes.c_int32)]
+
+
+class SisoDims(ctypes.Structure):
+    """sbce_siso_dims (include/sbce.h): the batched soft-in / soft-out decoder, sbce_siso_decode."""
+    _fields_ = [("batch", ctypes.c_int32), ("n_info", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("n", ctypes.c_int32), ("gen", ctypes.c_int32 * 3), ("flags", ctypes.c_int32)]
+
+
+class SisoPtrs(ctypes.Structure):
+    _fields_ = [("lc", ctypes.c_void_p), ("la_u", ctypes.c_void_p), ("perm", ctypes.c_void_p),
+                ("u_true", ctypes.c_void_p), ("lapp_u", ctypes.c_void_p),
+                ("u_hat", ctypes.c_void_p), ("le_c", ctypes.c_void_p), ("err", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
 
 
 _lib = None
@@ -274,6 +289,12 @@ def load(path=None):
                                   ctypes.c_int, ctypes.c_int, ctypes.POINTER(PriorOpts),
                                   ctypes.POINTER(NoiseOpts), ctypes.POINTER(ConvOpts),
                                   ctypes.c_void_p]
+    lib.sbce_siso_workspace_bytes.restype = ctypes.c_int
+    lib.sbce_siso_workspace_bytes.argtypes = [ctypes.POINTER(SisoDims),
+                                              ctypes.POINTER(ctypes.c_size_t)]
+    lib.sbce_siso_decode.restype = ctypes.c_int
+    lib.sbce_siso_decode.argtypes = [ctypes.POINTER(SisoDims), ctypes.POINTER(SisoPtrs),
+                                     ctypes.c_void_p]
     if lib.sbce_abi_version() != SBCE_ABI_VERSION:
         raise SbceUnavailable("libsbce ABI version mismatch")
     if path is None:

@@ -1033,6 +1033,19 @@ int sbce_debug_chol_skip(int mask) {
 #endif
 }
 
+// Diagnostic, not part of include/sbce.h: the decoder kernel as one wave per codeword group
+// (alpha over every step, then beta with the outputs) instead of the two-wave split, for the A/B
+// timing of tools/siso_bench.py; the results are bitwise the same.
+int sbce_debug_siso_onewave(int on) {
+#if SBCE_AB
+    siso_debug_onewave(on);
+    return SBCE_OK;
+#else
+    (void)on;
+    return SBCE_EUNSUPPORTED;                        // libsbce_ab.so only
+#endif
+}
+
 // Diagnostic, not part of include/sbce.h: one piece of the M-step for kernel timing (bench.py's
 // dominant-kernel roofline), from the given moments: phase 0 = the pilot factorisation (once per
 // EM run), 1 = the R build alone (the MFMA Hermitian build rbuild_herm_kernel when n_tx is 4 or
@@ -1305,6 +1318,58 @@ int sbce_detect_linear_prior(const sbce_linear_dims* d, const sbce_linear_ptrs* 
     a.sigma2 = d->sigma2; a.es = d->es;
     return hip_rc(la ? launch_detect_linear_prior(a, la, (hipStream_t)hip_stream)
                      : launch_detect_linear(a, (hipStream_t)hip_stream));
+}
+
+// The checks of sbce_siso_dims, in the header's order; n_steps on success
+static int siso_check_dims(const sbce_siso_dims* d, int* n_steps) {
+    if (!d) return SBCE_EINVAL;
+    if (d->batch < 1 || d->n_info < 1) return SBCE_EINVAL;
+    if (d->flags & ~(SBCE_DETECT_MAXLOG | SBCE_SISO_TERMINATED)) return SBCE_EINVAL;
+    if (!siso_supported(d->k, d->n)) return SBCE_EUNSUPPORTED;
+    for (int j = 0; j < d->n; ++j) {
+        const int g = d->gen[j];
+        if (g < 0 || (g >> d->k) || !((g >> (d->k - 1)) & 1) || !(g & 1)) return SBCE_EINVAL;
+    }
+    const long long T = (long long)d->n_info + ((d->flags & SBCE_SISO_TERMINATED) ? d->k - 1 : 0);
+    if (T > kSisoMaxSteps) return SBCE_EUNSUPPORTED;
+    *n_steps = (int)T;
+    return SBCE_OK;
+}
+
+int sbce_siso_workspace_bytes(const sbce_siso_dims* d, size_t* bytes) {
+    if (!bytes) return SBCE_EINVAL;
+    int T = 0;
+    const int rc = siso_check_dims(d, &T);
+    if (rc != SBCE_OK) return rc;
+    *bytes = siso_ws_bytes(d->batch, d->k, T);
+    return SBCE_OK;
+}
+
+int sbce_siso_decode(const sbce_siso_dims* d, const sbce_siso_ptrs* p, void* hip_stream) {
+    if (!d || !p || !p->lc) return SBCE_EINVAL;
+    int T = 0;
+    const int rc = siso_check_dims(d, &T);
+    if (rc != SBCE_OK) return rc;
+    if (p->err && !p->u_true) return SBCE_EINVAL;
+    if (!p->lapp_u && !p->u_hat && !p->le_c && !p->err) return SBCE_EINVAL;
+    if (!p->workspace || !aligned16(p->workspace)) return SBCE_EINVAL;
+    if (((uintptr_t)p->lc & 7) || ((uintptr_t)p->la_u & 7) || ((uintptr_t)p->lapp_u & 7) ||
+        ((uintptr_t)p->le_c & 7))
+        return SBCE_EINVAL;
+    if (((uintptr_t)p->perm & 3) || ((uintptr_t)p->u_true & 3) || ((uintptr_t)p->u_hat & 3) ||
+        ((uintptr_t)p->err & 3))
+        return SBCE_EINVAL;
+    if (p->workspace_bytes < siso_ws_bytes(d->batch, d->k, T)) return SBCE_EWORKSPACE;
+    clear_stale_error();
+    SisoArgs a{};
+    a.lc = p->lc; a.la = p->la_u; a.perm = p->perm; a.utrue = p->u_true;
+    a.lapp = p->lapp_u; a.uhat = p->u_hat; a.lec = p->le_c; a.err = p->err;
+    a.ws = (double*)p->workspace;
+    a.B = d->batch; a.ninfo = d->n_info; a.T = T; a.K = d->k; a.N = d->n;
+    for (int j = 0; j < 3; ++j) a.g[j] = j < d->n ? d->gen[j] : 0;
+    a.term = (d->flags & SBCE_SISO_TERMINATED) ? 1 : 0;
+    a.maxlog = (d->flags & SBCE_DETECT_MAXLOG) ? 1 : 0;
+    return hip_rc(launch_siso(a, (hipStream_t)hip_stream));
 }
 
 }  // extern "C"

@@ -807,4 +807,27 @@ size_t crb_dinv_bytes(const Problem& pb);
 hipError_t launch_crb(const Problem& pb, cd* R, cd* dinv, const cd* h_true, const sbce_crb_opts& o,
                       int32_t* status, hipStream_t s);
 
+// Soft-in / soft-out decoder (siso.hip, sbce_siso_decode): one launch per call, preceded by a small
+// zeroing kernel when err is set
+struct SisoArgs {
+    const double* lc;        // [B][T*N]
+    const double* la;        // [B][ninfo] or null
+    const int32_t* perm;     // [T*N] or null
+    const int32_t* utrue;    // [B][ninfo] or null
+    double* lapp;            // [B][ninfo] or null
+    int32_t* uhat;           // [B][ninfo] or null
+    double* lec;             // [B][T*N] or null
+    int32_t* err;            // [B] or null (zeroed before the launch)
+    double* ws;              // [siso_groups][T][64] metric rows
+    int B, ninfo, T, K, N;   // T = n_steps
+    int g[3];                // generators (g[2] unused at N = 2)
+    int term, maxlog;
+};
+constexpr int kSisoMaxSteps = 16384;
+bool siso_supported(int K, int N);            // K 3..7, N 2..3
+long long siso_groups(int B, int K);          // workgroups: 64 / 2^(K-1) codewords each
+size_t siso_ws_bytes(int B, int K, int T);
+hipError_t launch_siso(const SisoArgs& a, hipStream_t s);
+void siso_debug_onewave(int on);   // A/B build: the one-wave arm of the decoder kernel (same bits)
+
 }  // namespace sbce

@@ -1333,6 +1333,138 @@ def crb_batch(y_d, y_p, psi_d, u_p, cons, n_tx, sigma2, kind="genie", m=None, S=
             if k in want or k in ("tr_inv", "status", "bound")}
 
 
+# ------------------------------------------------------------------ decoder and the turbo loop
+_WANT_SISO = ("le_c", "lapp_u", "u_hat")
+
+
+def _f64dev(torch, x):
+    """A float64 input as a contiguous CUDA tensor (None stays None)."""
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor):
+        return x.to(device="cuda", dtype=torch.float64).contiguous()
+    return _dev(torch, x, np.float64)
+
+
+def _i32dev(torch, x):
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor):
+        return x.to(device="cuda", dtype=torch.int32).contiguous()
+    return _dev(torch, x, np.int32)
+
+
+def siso_decode_batch(lc, code, prior_u=None, perm=None, u_true=None, maxlog=False,
+                      want=_WANT_SISO, return_device=False, ws_fill=None):
+    """Soft-in / soft-out decoding of a batch of codewords: ONE sbce_siso_decode call (the BCJR
+    kernel of csrc/siso.hip, preceded by a small zeroing kernel when err is produced).
+
+    lc (B, n_steps*n): L-values log(P(bit = 0) / P(bit = 1)) of the received coded bits, e.g. a
+    detector's flattened ``llr``; code: a codec.ConvCode; prior_u (B, n_info): a-priori L-values
+    of the information bits; perm (n_steps*n,) int32: coded bit k sits at position perm[k] of lc
+    and of le_c (codec.random_interleaver; a bijection, not checked on the device); u_true
+    (B, n_info) 0/1: also err (B,) int32, the bit errors of u_hat; maxlog: max-log-MAP.  NaN is
+    read as 0 and every value is clamped to +-64.  Inputs may be numpy arrays or CUDA tensors
+    (used in place).  ws_fill: a byte the workspace is filled with first (tests).
+    Returns a dict with the outputs named in ``want``: le_c (B, n_steps*n) the EXTRINSIC L-values
+    of the coded bits (what the detector takes as prior_llr), lapp_u (B, n_info) the a-posteriori
+    L-values and u_hat (B, n_info) int32 the decisions."""
+    torch = _torch()
+    lib = _lib.load()
+    bad = set(want) - set(_WANT_SISO)
+    if bad:
+        raise ValueError(f"unknown outputs {sorted(bad)}")
+    Lc, La, Pm, Ut = (_f64dev(torch, lc), _f64dev(torch, prior_u), _i32dev(torch, perm),
+                      _i32dev(torch, u_true))
+    if Lc.dim() != 2:
+        raise ValueError("lc must be (B, n_steps*n)")
+    B, nc = Lc.shape
+    n_info = code.n_info_for(nc)
+    if La is not None and tuple(La.shape) != (B, n_info):
+        raise ValueError(f"prior_u shape {tuple(La.shape)} != {(B, n_info)}")
+    if Ut is not None and tuple(Ut.shape) != (B, n_info):
+        raise ValueError(f"u_true shape {tuple(Ut.shape)} != {(B, n_info)}")
+    if Pm is not None and tuple(Pm.shape) != (nc,):
+        raise ValueError(f"perm shape {tuple(Pm.shape)} != {(nc,)}")
+    gens = tuple(code.generators) + (0,) * (3 - code.n)
+    flags = ((_lib.SBCE_DETECT_MAXLOG if maxlog else 0) |
+             (_lib.SBCE_SISO_TERMINATED if code.terminated else 0))
+    dims = _lib.SisoDims(B, n_info, code.K, code.n, (ctypes.c_int32 * 3)(*gens), flags)
+    f64, i32 = torch.float64, torch.int32
+    shapes = {"le_c": ((B, nc), f64), "lapp_u": ((B, n_info), f64), "u_hat": ((B, n_info), i32)}
+    out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device="cuda")
+           for k in _WANT_SISO if k in want}
+    if Ut is not None:
+        out["err"] = torch.empty(B, dtype=i32, device="cuda")
+    ws = _scratch(torch, lib.sbce_siso_workspace_bytes, "sbce_siso_workspace_bytes",
+                  ctypes.byref(dims))
+    if ws_fill is not None:
+        ws.fill_(int(ws_fill))
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    ptrs = _lib.SisoPtrs(Lc.data_ptr(), ptr(La), ptr(Pm), ptr(Ut), ptr(out.get("lapp_u")),
+                         ptr(out.get("u_hat")), ptr(out.get("le_c")), ptr(out.get("err")),
+                         ws.data_ptr(), ws.numel())
+    _lib.check(lib.sbce_siso_decode(dims, ptrs, torch.cuda.current_stream().cuda_stream),
+               "sbce_siso_decode")
+    return _result(torch, out, return_device)      # the workspace is used in stream order
+
+
+def turbo_em_batch(y_d, y_p, psi_d, u_p, cons, varn, theta0, n_tx, code, perm, outer=4, itera=3,
+                   ep_passes=None, labels=None, noise="true", u_true=None, h_true=None):
+    """The code-aided (turbo) loop: channel estimation, detection and decoding exchanging soft
+    information.  With la^0 = no prior and theta_0 = theta0, for k = 1..outer:
+      theta_k = em_batch(mode="ep", prior_llr=la^{k-1}, theta0=theta_{k-1}), ``itera`` iterations
+      llr     = detect_linear_prior_batch(theta_k, la^{k-1}): the detector's extrinsic L-values
+      la^k    = siso_decode_batch(llr flattened per trial, perm)'s le_c, reshaped to
+                (B, T_d, n_tx, log2 M); u_hat the decoder's decisions
+    One codeword spans the T_d n_tx log2 M bits of a trial: bit i of stream a of symbol t is
+    position (t n_tx + a) log2 M + i, and coded bit k travels at position perm[k].
+    varn: the noise variance the data carry.  noise="true": the EM is given sqrt(varn), whose
+    square its posterior divides by, and the detector varn (exit_chart.py's convention);
+    noise="em": both are given varn as the reference's EM parameter.  The L-values stay on the
+    device between the three calls.
+    Returns a list of ``outer`` dicts of numpy arrays: theta (B,K), u_hat (B,n_info) and, with
+    u_true (B,n_info), bit_errors (B,); with h_true (B,K), nmse (B,)."""
+    torch = _torch()
+    if noise not in ("em", "true"):
+        raise ValueError("noise must be 'em' or 'true'")
+    n_tx = int(n_tx)
+    Yd, Yp, Ps, Up, Cs, theta = (_cdev(torch, x) for x in (y_d, y_p, psi_d, u_p, cons, theta0))
+    Ht = _cdev(torch, h_true)
+    B, T_d = Yd.shape[0], Yd.shape[1]
+    M = Cs.shape[0]
+    lgM = max(int(M - 1).bit_length(), 1)
+    code.n_info_for(T_d * n_tx * lgM)                  # raises when a trial is no codeword
+    lab_np = _detect_labels(M, labels, True)
+    es = _linear_es(torch, cons, None)
+    Pm, Ut = _i32dev(torch, perm), _i32dev(torch, u_true)
+    v0, Vt = _varn_arg(torch, varn, B)
+    varn_em = varn if noise == "em" else (float(np.sqrt(v0)) if Vt is None else torch.sqrt(Vt))
+    kind = "ep" if ep_passes is None else ("ep", int(ep_passes))
+    la, out = None, []
+    for _ in range(int(outer)):
+        em = em_batch(Yd, Yp, Ps, Up, Cs, varn_em, int(itera), theta, mode="ep",
+                      ep_passes=ep_passes, prior_llr=la, labels=lab_np, return_device=True)
+        theta = em["theta"]
+        det = detect_linear_prior_batch(Yd, Ps, Cs, theta, varn, n_tx, la, kind=kind, es=es,
+                                        labels=lab_np, noise=noise, want=("llr",),
+                                        return_device=True)
+        dec = siso_decode_batch(det["llr"].reshape(B, -1), code, perm=Pm, u_true=Ut,
+                                want=("le_c", "u_hat"), return_device=True)
+        la = dec["le_c"].reshape(B, T_d, n_tx, lgM)
+        res = dict(theta=theta, u_hat=dec["u_hat"])
+        if Ut is not None:
+            res["bit_errors"] = dec["err"]
+        if Ht is not None:
+            res["nmse"] = nmse_batch(theta, Ht)
+        out.append(res)
+    torch.cuda.current_stream().synchronize()
+    return [{k: v.cpu().numpy() for k, v in r.items()} for r in out]
+
+
 class EMEngine:
     """Pre-allocated device state for repeated batched EM runs (benchmark / sweeps).
 

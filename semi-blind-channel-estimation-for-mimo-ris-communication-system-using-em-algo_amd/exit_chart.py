@@ -6,7 +6,9 @@ the true channel and from the channel the code-aided EM estimates with the same 
 L-values.  With --nmse: the NMSE of that EM against I_A, beside the pilot-only and the genie
 Cramer-Rao bounds of crb_batch -- the two ends the curve runs between (the reference's DFT pilot
 phases repeat the direct path's row, so on this data the pilot-only bound is infinite: the
-pilots alone do not identify the channel)."""
+pilots alone do not identify the channel).  With --decoder: the transfer curve of the BCJR decoder
+(siso_decode_batch) for one codeword per trial, I_E of its extrinsic coded-bit L-values against
+I_A of the L-values it is given."""
 import argparse
 
 import numpy as np
@@ -33,6 +35,13 @@ def main():
                          "the reference's EM posterior (em)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--nmse", action="store_true")
+    ap.add_argument("--decoder", action="store_true",
+                    help="also the decoder's transfer curve: I_E of siso_decode_batch's le_c "
+                         "against I_A of consistent-Gaussian L-values on the coded bits (the curve "
+                         "that must fit under the detector's, axes swapped)")
+    ap.add_argument("--generators", type=lambda s: int(s, 8), nargs="+", default=[0o133, 0o171],
+                    help="--decoder: octal generators, 2 or 3")
+    ap.add_argument("--K", type=int, default=7)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     pkg = package()
@@ -70,6 +79,18 @@ def main():
         out = None if a.out is None else a.out.replace(".npz", "") + "_nmse.npz"
         report("I_A", a.IA, {k: np.array(v) for k, v in nm.items()}, out,
                "code-aided EM between the pilot-only and the genie bound")
+    if a.decoder:
+        # one codeword per trial, of the length the detector's llr of a trial has
+        code = pkg.ConvCode(a.generators, a.K, True)
+        nc = a.T_d * a.n_tx * int(a.M - 1).bit_length()
+        drng = np.random.default_rng(a.seed + 2)
+        c = code.encode(drng.integers(0, 2, (a.monte_iter, code.n_info_for(nc))))
+        ie = [q.bit_mutual_information(
+            pkg.siso_decode_batch(q.prior_llr_gaussian(c, ia, drng), code, want=("le_c",))["le_c"], c)
+            for ia in a.IA]
+        out = None if a.out is None else a.out.replace(".npz", "") + "_decoder.npz"
+        report("I_A", a.IA, {f"I_E decoder K={a.K}": np.array(ie)}, out,
+               "EXIT transfer curve of the decoder", ylabel="I_E", logy=False)
 
 
 if __name__ == "__main__":

@@ -43,6 +43,23 @@ def bits_of(labels):
     return ((labels[:, None] >> np.arange(m)[None, :]) & 1).astype(np.int8)
 
 
+def map_bits(bits, cons, labels):
+    """Bits to table points: bits (..., log2 M) of 0/1, LSB first under ``labels`` -> (...) complex,
+    the point s with bits_of(labels)[s] == bits; the inverse of ``bits_of(labels)[idx]``."""
+    cons = np.asarray(cons, dtype=complex).reshape(-1)
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    bits = np.asarray(bits)
+    m = max(int(cons.size - 1).bit_length(), 1)
+    if labels.size != cons.size or bits.shape[-1] != m:
+        raise ValueError(f"bits must end in log2 M = {m} and labels have M = {cons.size} entries")
+    if np.any((bits != 0) & (bits != 1)) or not np.array_equal(np.sort(labels), np.arange(cons.size)):
+        raise ValueError("bits must be 0/1 and labels a permutation of 0..M-1")
+    index_of = np.empty(cons.size, dtype=np.int64)
+    index_of[labels] = np.arange(cons.size)
+    word = (bits.astype(np.int64) << np.arange(m)).sum(axis=-1)
+    return cons[index_of[word]]
+
+
 def prior_llr_known(x, cons, labels):
     """A-priori bit L-values log(P(bit = 0) / P(bit = 1)) that mark the symbols ``x`` (any shape,
     each the table point nearest to it) as known: +inf where the symbol's bit is 0, -inf where it

@@ -254,12 +254,14 @@ def snr_to_varn(snr_db, power=10.0):
 # ----------------------------------------------------------------- batch generator
 
 def synthetic_batch(B, n_tx, n_rx, N, T_p, T_d, M, varn, seed=0, varh=1.0, direct=True,
-                    pilot="dft_n", pinv="numpy"):
+                    pilot="dft_n", pinv="numpy", x_d=None):
     """Vectorised Monte-Carlo batch with the reference's distributions.  pinv: the cut of
     h_initial's pseudo-inverse, "numpy" (np.linalg.pinv's 1e-15, Proposed_method_NMSEvsTp.py:129)
     or "scipy" (max(M, N) eps, the scipy.linalg.pinv of all_detectorsvsTd.py:341; see
     initial_estimate).  With T_p > N the DFT pilot phases repeat and the numpy cut keeps
-    rounding-level singular values: theta_0 ~ 1e13.
+    rounding-level singular values: theta_0 ~ 1e13.  x_d (B,T_d,n_tx): the caller's data symbols
+    (e.g. qam.map_bits of a codeword) instead of the generator's; its own draw is still made and
+    discarded, so every other array keeps the bits of the default call.
 
     Returns a dict of batch-major arrays in the C-ABI layout:
       y_d (B,T_d,n_rx), y_p (B,T_p,n_rx), psi_d (B,T_d,P), u_p (B,T_p,L),
@@ -278,7 +280,13 @@ def synthetic_batch(B, n_tx, n_rx, N, T_p, T_d, M, varn, seed=0, varh=1.0, direc
     Hc = np.concatenate(blocks, axis=1)                      # (B, P, n_tx, n_rx)
     P = Hc.shape[1]
     h = Hc.reshape(B, -1)
-    x_d = cons[g.integers(0, M, (B, T_d, n_tx))]
+    drawn = cons[g.integers(0, M, (B, T_d, n_tx))]
+    if x_d is None:
+        x_d = drawn
+    else:
+        x_d = np.ascontiguousarray(x_d, dtype=complex)
+        if x_d.shape != drawn.shape:
+            raise ValueError(f"x_d shape {x_d.shape} != {drawn.shape}")
     x_p = cons[g.integers(0, M, (B, T_p, n_tx))]
     ph = g.uniform(0, 2 * np.pi, (B, T_d, N))
     psi_d = np.exp(1j * ph)
